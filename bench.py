@@ -19,6 +19,10 @@ in-repo numbers, so `vs_baseline` is null.
 Usage (driver contract):
     python bench.py --gpus N --steps K --warmup W
     torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1)
+
+A plain run sets up, warms up, times K steps and prints one JSON line;
+``--dump-outputs DIR`` also saves what the last timed step computed,
+and ``--full`` is the home of any secondary measurement (none today).
 """
 
 import argparse
@@ -57,7 +61,49 @@ def parse_args():
                     help="fp8(e4m3) Z tile between corr and Gram "
                          "(BRAINIAK_FP8=1 equivalent)")
     ap.add_argument("--device", default=None)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last "
+                         "timed step computed to DIR/<name>.npy "
+                         "(float32): accuracy.npy = per-voxel CV "
+                         "accuracy [voxels_per_step]; with --no-cv "
+                         "kernels.npy = the [n, E, E] Gram matrices "
+                         "(a fixed seeded voxel sample when they "
+                         "exceed 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline "
+                         "figure (secondary measurements and checks). "
+                         "This benchmark currently has none, so the "
+                         "flag changes nothing")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+# 64 MB cap on everything --dump-outputs writes, with room for headers
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000
+
+
+def dump_outputs(outputs, out_dir, rank):
+    """Write {name: tensor/array} as float32 .npy files, at most
+    DUMP_BUDGET_BYTES in all.  An oversized array is cut to a fixed
+    seeded sample of its leading (voxel) axis, so two builds given the
+    same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES // max(len(outputs), 1)
+    for name, val in outputs.items():
+        if not torch.is_tensor(val):
+            val = torch.as_tensor(np.asarray(val))
+        n = val.shape[0]
+        row_bytes = 4 * max(val[0].numel(), 1)
+        keep = budget // row_bytes
+        if n > keep:
+            idx = np.sort(np.random.default_rng(0).choice(
+                n, size=keep, replace=False))
+            val = val[torch.as_tensor(idx, device=val.device)]
+        arr = val.detach().to(torch.float32).cpu().numpy()
+        suffix = "" if rank == 0 else f".rank{rank}"
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 def make_synthetic_epochs(rng, n_epochs, length, voxels, device):
@@ -89,6 +135,7 @@ def main():
         backend = "gloo"
     if args.device:
         device = torch.device(args.device)
+        backend = "nccl" if device.type == "cuda" else "gloo"
 
     if distributed:
         import torch.distributed as dist
@@ -127,7 +174,9 @@ def main():
         vps = min(vps, 256)
         chunk = min(chunk, 128)
 
-    def one_step(step_idx):
+    last = {}    # --dump-outputs: what the final timed step computed
+
+    def one_step(step_idx, keep=False):
         # rank-interleaved rotation: ranks score disjoint voxel ranges
         # each step, exactly how VoxelSelector shards a whole-brain run
         start0 = ((step_idx * world + rank) * vps) % V
@@ -153,7 +202,10 @@ def main():
 
             pipeline._duo_pipeline(chunks, consumer=consume)
             torch.cuda.current_stream(device).wait_stream(cv_stream)
-            return float(torch.cat(accs).mean().cpu())
+            acc = torch.cat(accs)
+            if keep:
+                last["accuracy"] = acc
+            return float(acc.mean().cpu())
         kernels = pipeline.pipelined_kernel_matrices(chunks)
         if not args.no_cv:
             if device.type == "cuda":
@@ -167,7 +219,11 @@ def main():
             else:  # CPU smoke: tiny sklearn sample to keep runtime sane
                 accs = cross_validate_voxels(kernels[:8], labels,
                                              args.num_folds)
+            if keep:
+                last["accuracy"] = accs
             return float(np.mean(accs))
+        if keep:
+            last["kernels"] = kernels
         return float(kernels[0].float().mean())
 
     def barrier_sync():
@@ -184,7 +240,9 @@ def main():
     t0 = time.perf_counter()
     sink = 0.0
     for k in range(args.steps):
-        sink += one_step(args.warmup + k)
+        sink += one_step(args.warmup + k,
+                         keep=bool(args.dump_outputs)
+                         and k == args.steps - 1)
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
@@ -195,6 +253,9 @@ def main():
                          device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+
+    if args.dump_outputs:
+        dump_outputs(last, args.dump_outputs, rank)
 
     ms_per_step = elapsed * 1000.0 / args.steps
     pairs_per_sec = (vps * world * V) / (elapsed / args.steps)

@@ -175,7 +175,7 @@ def test_srm_batched_polar_many_matches_loop(seeded_rng):
 def test_srm_w_orthogonality_and_shapes(seeded_rng):
     from brainiak_amd.funcalign.srm import SRM
     data = [seeded_rng.randn(30 + 5 * i, 40) for i in range(3)]
-    m = SRM(n_iter=6, features=4, rand_seed=0)
+    m = SRM(n_iter=6, features=4, rand_seed=0, device="cpu")
     m.fit(data)
     assert m.s_.shape == (4, 40)
     for i, w in enumerate(m.w_):
