@@ -65,7 +65,7 @@ def main():
           "voxels": args.voxels, "events": args.events,
           "global_batch": regions, "seq_len": args.trs,
           "parallelism": f"region-sharded dp{world}"})
-    teardown()
+    teardown(world)
 
 
 if __name__ == "__main__":

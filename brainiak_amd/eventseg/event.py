@@ -18,6 +18,13 @@ reference's exp/dot/rescale round trip — numerically it is at least as
 stable and needs no masked-log inside the recursion (transition zeros
 enter once as -inf in the log transition matrix).
 
+On the GPU (K <= 64) that recursion is a single HIP launch,
+``ops.hmm_forward_backward``: one wavefront per sequence walks the
+sparse chain graph (self loop + one advance edge per state) with the
+time loop inside the kernel, so an E-step no longer costs a few thousand
+kernel launches.  The torch T-loop remains the CPU path and the K > 64
+path.
+
 The reference's Cython ``masked_log`` helper (eventseg/_utils.pyx:27-54)
 survives as ``brainiak_amd.ops.masked_log`` for the public quirk surface
 (prior vectors with exact zeros).
@@ -28,6 +35,7 @@ continuous narrative perception and memory", Neuron 95(3).
 
 import itertools
 import logging
+import os
 
 import numpy as np
 import torch
@@ -39,6 +47,8 @@ logger = logging.getLogger(__name__)
 __all__ = ["EventSegment"]
 
 _NEG_INF = float("-inf")
+# ops.hmm_forward_backward maps one event state per wavefront lane
+_HIP_FB_MAX_K = 64
 
 
 class NotFittedError(ValueError):
@@ -71,6 +81,14 @@ class _ChainGraph:
     p_trans = (chain_len - 1) / T  — the reference's hazard choice
     (ref event.py:284-369), which makes the expected dwell time span the
     sequence.
+
+    Besides the dense ``P``/``logP`` the same graph is kept sparsely,
+    as per-event vectors of length K on the compute device (what the HIP
+    recursion ``ops.hmm_forward_backward`` consumes): ``log_self[k]`` /
+    ``log_adv[k]`` are the log self-loop / leave probabilities of state
+    k, ``pred[k]`` / ``succ[k]`` (int32) the previous / next member of
+    k's chain, -1 at a chain head / tail.  Chains may interleave, so
+    these are arbitrary gathers, not k-1 / k+1.
     """
 
     def __init__(self, event_chains, t, device, dtype=torch.float64):
@@ -82,6 +100,10 @@ class _ChainGraph:
         start = torch.zeros(k + 1, dtype=dtype)
         end = torch.zeros(k + 1, dtype=dtype)
         P = torch.zeros((k + 1, k + 1), dtype=dtype)
+        p_self = torch.zeros(k, dtype=dtype)
+        p_adv = torch.zeros(k, dtype=dtype)
+        pred = torch.full((k,), -1, dtype=torch.int32)
+        succ = torch.full((k,), -1, dtype=torch.int32)
         for c in range(n_chains):
             members = np.flatnonzero(labels == c)
             start[members[0]] = 1.0 / n_chains
@@ -93,6 +115,11 @@ class _ChainGraph:
                 P[s, s] = 1 - p_trans
                 nxt = members[j + 1] if j + 1 < len(members) else k
                 P[s, nxt] = P[s, nxt] + p_trans
+                p_self[s] = 1 - p_trans
+                p_adv[s] = p_trans
+                if j + 1 < len(members):
+                    succ[s] = int(nxt)
+                    pred[nxt] = int(s)
         P[k, k] = 1.0
 
         self.p_start = start.numpy()
@@ -104,6 +131,10 @@ class _ChainGraph:
         self.log_end = ops.masked_log(end).to(device)
         self.logP = ops.masked_log(P.reshape(-1)).reshape(k + 1,
                                                           k + 1).to(device)
+        self.log_self = ops.masked_log(p_self).to(device)
+        self.log_adv = ops.masked_log(p_adv).to(device)
+        self.pred = pred.to(device)
+        self.succ = succ.to(device)
 
 
 class EventSegment:
@@ -146,6 +177,20 @@ class EventSegment:
 
     # -- batched core ------------------------------------------------------
 
+    def _chain_graph(self, t, device):
+        """``_ChainGraph`` for (event_chains, t, device), kept from the
+        previous call: every E-step of a fit asks for the same one, and
+        rebuilding it costs a Python loop over K plus a handful of
+        host-to-device copies."""
+        chains = np.asarray(self.event_chains)
+        key = (chains.dtype.str, chains.shape, chains.tobytes(), int(t),
+               str(device))
+        cached = self.__dict__.get("_graph_cache")
+        if cached is None or cached[0] != key:
+            cached = (key, _ChainGraph(chains, t, device))
+            self.__dict__["_graph_cache"] = cached
+        return cached[1]
+
     def _forward_backward_batch(self, logprob):
         """Batched log-space forward-backward.
 
@@ -159,17 +204,30 @@ class EventSegment:
         log_gamma : torch [B, T, K] row-normalized posteriors.
         ll : torch [B] sequence log-likelihoods.
 
-        Everything is pure log space: one batched ``logsumexp``
-        contraction against the [K+1, K+1] log transition matrix per
-        timestep, no per-step rescaling needed (fp64 headroom is vast at
-        fMRI sequence lengths).
+        Everything is pure log space, no per-step rescaling needed
+        (fp64 headroom is vast at fMRI sequence lengths).  On the GPU
+        with K <= 64 the whole pass is one HIP launch over the sparse
+        chain vectors (``ops.hmm_forward_backward``;
+        ``BRAINIAK_EVENTSEG_FB=torch`` forces the torch path); otherwise
+        it is one batched ``logsumexp`` contraction against the
+        [K+1, K+1] log transition matrix per timestep.
         """
         B, T, K = logprob.shape
         dev = logprob.device
-        graph = _ChainGraph(self.event_chains, T, dev)
+        graph = self._chain_graph(T, dev)
         # compat surface: the reference exposes these after any FB pass
-        self.p_start, self.p_end, self.P = (graph.p_start, graph.p_end,
-                                            graph.P)
+        # (copies: the graph itself is reused between calls)
+        self.p_start, self.p_end, self.P = (graph.p_start.copy(),
+                                            graph.p_end.copy(),
+                                            graph.P.copy())
+
+        if (logprob.is_cuda and K <= _HIP_FB_MAX_K
+                and os.environ.get("BRAINIAK_EVENTSEG_FB", "") != "torch"
+                and ops.require_hip()):
+            lp = logprob.to(torch.float64).contiguous()
+            return ops.hmm_forward_backward(
+                lp, graph.log_start, graph.log_end, graph.log_self,
+                graph.log_adv, graph.pred, graph.succ)
 
         obs = torch.full((B, T, K + 1), _NEG_INF, dtype=torch.float64,
                          device=dev)

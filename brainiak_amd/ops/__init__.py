@@ -13,6 +13,8 @@ factoranalysis/tfa_extension.cpp, eventseg/_utils.pyx):
                           polar factor for SRM (srm.py:595-606 class)
  - ``tfa_factor`` / ``tfa_recon`` — TFA RBF factor matrix + residual
                           (N8/N9)
+ - ``hmm_forward_backward`` — single-launch log-space forward-backward
+                          over EventSegment's event chains (N10)
 
 Build: ``python setup.py build_ext --inplace`` (hipcc, gfx950) or
 ``__graft_entry__.build()``.  The extension is REQUIRED whenever CUDA
@@ -36,6 +38,8 @@ __all__ = [
     "fcma_normalize_",
     "has_fused_gram",
     "has_hip",
+    "hmm_fb_tile",
+    "hmm_forward_backward",
     "isfc_accum_",
     "stencil3d",
     "load_extension",
@@ -216,6 +220,36 @@ def tfa_recon(X: torch.Tensor, W: torch.Tensor, F: torch.Tensor,
               scale: float) -> torch.Tensor:
     """Flattened residual scale*(X - F·W) for TFA least-squares."""
     return _ext().tfa_recon(X, W, F, float(scale))
+
+
+# ---------------------------------------------------------------------------
+# EventSegment forward-backward (N10)
+# ---------------------------------------------------------------------------
+
+def hmm_forward_backward(logprob: torch.Tensor, log_start: torch.Tensor,
+                         log_end: torch.Tensor, log_self: torch.Tensor,
+                         log_adv: torch.Tensor, pred: torch.Tensor,
+                         succ: torch.Tensor):
+    """Log-space HMM forward-backward over left-to-right event chains in
+    one launch (one wavefront per sequence, lane k = event k; K <= 64).
+
+    logprob [B, T, K] fp64 observation log-probabilities; log_start /
+    log_end fp64 with at least K entries (a trailing sink entry is
+    ignored); log_self / log_adv fp64 [K] (self-loop and advance
+    log-probabilities); pred / succ int32 [K] (previous / next member of
+    k's chain, -1 at a chain head / tail).  All on the GPU.
+
+    Returns (log_gamma [B, T, K] row-normalized log posteriors, ll [B]).
+    """
+    lg, ll = _ext().hmm_forward_backward(logprob, log_start, log_end,
+                                         log_self, log_adv, pred, succ)
+    return lg, ll
+
+
+def hmm_fb_tile() -> int:
+    """Timesteps per streamed tile of the forward-backward kernel (the
+    sizes around which its tile-tail paths switch)."""
+    return int(_ext().hmm_fb_tile())
 
 
 # ---------------------------------------------------------------------------

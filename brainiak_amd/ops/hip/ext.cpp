@@ -1,12 +1,15 @@
 // Torch bindings for the brainiak_amd HIP/CDNA4 kernels (gfx950).
 //
 // The device code lives in fcma_kernels.hip / procrustes.hip /
-// tfa_kernels.hip (hand-written HIP, MFMA/LDS — no library GEMMs on the
-// FCMA path); this file validates tensors, allocates outputs, and calls
-// the extern "C" launchers on the current stream.
+// tfa_kernels.hip / hmm_kernels.hip (hand-written HIP, MFMA/LDS — no
+// library GEMMs on the FCMA path); this file validates tensors,
+// allocates outputs, and calls the extern "C" launchers on the current
+// stream.
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+
+#include <climits>
 
 typedef long long ll;
 
@@ -51,6 +54,10 @@ void launch_stencil3d(const float*, const float*, float*, ll, int, int,
                       int, int, void*);
 void launch_fcma_fused_corr_gram(const void*, const void*, float*, ll,
                                  ll, ll, ll, ll, int, void*);
+void launch_hmm_fb(const double*, const double*, const double*,
+                   const double*, const double*, const int*, const int*,
+                   double*, double*, ll, int, int, void*);
+int hmm_fb_tile(void);
 }
 
 static void* cur_stream() {
@@ -564,7 +571,54 @@ torch::Tensor isfc_accum_(torch::Tensor acc, torch::Tensor M) {
     return acc;
 }
 
+std::vector<torch::Tensor> hmm_forward_backward(
+        torch::Tensor logprob, torch::Tensor log_start,
+        torch::Tensor log_end, torch::Tensor log_self,
+        torch::Tensor log_adv, torch::Tensor pred, torch::Tensor succ) {
+    // single-launch log-space forward-backward over the K event states
+    // of EventSegment's chain graph (hmm_kernels.hip::k_hmm_fb)
+    check_3d(logprob, torch::kFloat64, "logprob");
+    ll B = logprob.size(0), T = logprob.size(1), K = logprob.size(2);
+    TORCH_CHECK(K >= 1 && K <= 64, "hmm_forward_backward needs "
+                "1 <= K <= 64 event states (got ", K, ")");
+    TORCH_CHECK(T >= 1 && T <= INT_MAX / 64, "T out of range");
+    TORCH_CHECK(B <= INT_MAX, "too many sequences for one launch");
+    for (auto* v : {&log_start, &log_end, &log_self, &log_adv}) {
+        TORCH_CHECK(v->is_cuda() && v->is_contiguous() && v->dim() == 1
+                    && v->scalar_type() == torch::kFloat64
+                    && v->device() == logprob.device(),
+                    "chain vectors must be contiguous fp64 [>=K] on GPU");
+    }
+    // log_start / log_end may carry the sink entry after the K events
+    TORCH_CHECK(log_start.size(0) >= K && log_end.size(0) >= K,
+                "log_start/log_end must have at least K entries");
+    TORCH_CHECK(log_self.size(0) == K && log_adv.size(0) == K,
+                "log_self/log_adv must have K entries");
+    for (auto* v : {&pred, &succ}) {
+        TORCH_CHECK(v->is_cuda() && v->is_contiguous() && v->dim() == 1
+                    && v->scalar_type() == torch::kInt32
+                    && v->size(0) == K
+                    && v->device() == logprob.device(),
+                    "pred/succ must be contiguous int32 [K] on GPU");
+    }
+    auto log_gamma = torch::empty({B, T, K}, logprob.options());
+    auto llik = torch::empty({B}, logprob.options());
+    if (B == 0) return {log_gamma, llik};
+    launch_hmm_fb(logprob.data_ptr<double>(), log_start.data_ptr<double>(),
+                  log_end.data_ptr<double>(), log_self.data_ptr<double>(),
+                  log_adv.data_ptr<double>(), pred.data_ptr<int>(),
+                  succ.data_ptr<int>(), log_gamma.data_ptr<double>(),
+                  llik.data_ptr<double>(), B, (int)T, (int)K,
+                  cur_stream());
+    return {log_gamma, llik};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("hmm_forward_backward", &hmm_forward_backward,
+          "log-space HMM forward-backward over chain states "
+          "-> (log_gamma [B,T,K], ll [B])");
+    m.def("hmm_fb_tile", []() { return hmm_fb_tile(); },
+          "timesteps per streamed tile of k_hmm_fb");
     m.def("stencil3d", &stencil3d,
           "direct [K,K,K] valid conv over [B,X,Y,Z] (searchlight ball)");
     m.def("isfc_accum_", &isfc_accum_,
