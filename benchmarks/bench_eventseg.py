@@ -4,7 +4,13 @@ many searchlight-sized regions (the realistic whole-brain use: fit an
 EventSegment per region).  Metric: region-fits/s.
 
 One step = fitting ``--regions`` independent EventSegment models
-(ragged lengths grouped by the batched forward-backward)."""
+(ragged lengths grouped by the batched forward-backward).
+
+``--decode`` times inference instead: the models are fitted once outside
+the timed steps and one step is ``decode_regions`` (MAP event paths) over
+all regions; metric region-decodes/s.  ``--find-events`` times the
+marginal route to hard labels (``find_events_regions`` + argmax) the same
+way, for comparison."""
 
 import argparse
 import os
@@ -25,6 +31,13 @@ def main():
     ap.add_argument("--trs", type=int, default=200)
     ap.add_argument("--voxels", type=int, default=100)
     ap.add_argument("--events", type=int, default=8)
+    ap.add_argument("--decode", action="store_true",
+                    help="time decode_regions (MAP event paths) of "
+                         "models fitted once outside the timed steps; "
+                         "metric: region-decodes/s")
+    ap.add_argument("--find-events", action="store_true",
+                    help="like --decode, but time find_events_regions + "
+                         "argmax, the marginal route to hard labels")
     args = ap.parse_args()
 
     rank, world, device, _ = dist_setup()
@@ -46,6 +59,9 @@ def main():
 
     dev = str(device) if device.type == "cuda" else "cpu"
 
+    if args.decode or args.find_events:
+        return bench_decode(args, data, regions, dev, rank, world, device)
+
     batched = not os.environ.get("BRAINIAK_EVENTSEG_SEQ")
 
     def step(i):
@@ -64,6 +80,39 @@ def main():
          {"model": "eventseg", "regions": regions, "trs": args.trs,
           "voxels": args.voxels, "events": args.events,
           "global_batch": regions, "seq_len": args.trs,
+          "parallelism": f"region-sharded dp{world}"})
+    teardown(world)
+
+
+def bench_decode(args, data, regions, dev, rank, world, device):
+    """One step = hard labels for every region from models fitted once
+    up front: ``decode_regions`` (Viterbi), or with ``--find-events``
+    the argmax of ``find_events_regions``'s marginals."""
+    from brainiak_amd.eventseg.event import EventSegment
+
+    proto = EventSegment(args.events, n_iter=10, device=dev)
+    models = proto.fit_regions(data)
+
+    if args.decode:
+        def step(i):
+            proto.decode_regions(models, data)
+        metric = "eventseg_region_decodes_per_sec"
+    else:
+        def step(i):
+            segments, _ = proto.find_events_regions(models, data)
+            for seg in segments:
+                seg.argmax(axis=1)
+        metric = "eventseg_region_find_events_per_sec"
+
+    elapsed = timed_steps(step, args.steps, args.warmup, world, device)
+    per_sec = regions * world * args.steps / elapsed
+    emit(rank, metric, per_sec, "regions/s",
+         world, args.steps, args.warmup, elapsed, True, "weak", "fp64",
+         {"model": "eventseg", "regions": regions, "trs": args.trs,
+          "voxels": args.voxels, "events": args.events,
+          "global_batch": regions, "seq_len": args.trs,
+          "recursion": ("hip" if device.type == "cuda" and os.environ.get(
+              "BRAINIAK_EVENTSEG_FB", "") != "torch" else "torch"),
           "parallelism": f"region-sharded dp{world}"})
     teardown(world)
 

@@ -25,6 +25,14 @@ time loop inside the kernel, so an E-step no longer costs a few thousand
 kernel launches.  The torch T-loop remains the CPU path and the K > 64
 path.
 
+Hard labels (MI355X addition — no reference counterpart): ``decode`` /
+``decode_regions`` return the MAP event path (Viterbi) instead of the
+argmax of the posterior marginals that ``predict`` takes, which need not
+be a path of the model at all.  The max-plus recursion rides the same
+chain vectors and the same dispatch: ``ops.hmm_viterbi`` (one launch,
+back-pointers as one ballot word per timestep) on the GPU for K <= 64,
+a torch T-loop elsewhere, bit-identical to each other.
+
 The reference's Cython ``masked_log`` helper (eventseg/_utils.pyx:27-54)
 survives as ``brainiak_amd.ops.masked_log`` for the public quirk surface
 (prior vectors with exact zeros).
@@ -47,7 +55,8 @@ logger = logging.getLogger(__name__)
 __all__ = ["EventSegment"]
 
 _NEG_INF = float("-inf")
-# ops.hmm_forward_backward maps one event state per wavefront lane
+# ops.hmm_forward_backward / ops.hmm_viterbi map one event state per
+# wavefront lane
 _HIP_FB_MAX_K = 64
 
 
@@ -135,6 +144,39 @@ class _ChainGraph:
         self.log_adv = ops.masked_log(p_adv).to(device)
         self.pred = pred.to(device)
         self.succ = succ.to(device)
+
+
+def _viterbi_torch(lp, graph):
+    """The recursion of ``EventSegment._viterbi_batch`` as a T-loop of
+    batched torch ops over ``graph``'s chain vectors: lp fp64 [B, T, K]
+    -> (path int64 [B, T], score fp64 [B])."""
+    B, T, K = lp.shape
+    dev = lp.device
+    has_p = graph.pred >= 0                               # [K]
+    p = graph.pred.clamp_min(0).long()
+    adv_p = graph.log_adv[p]
+    ninf = torch.full((), _NEG_INF, dtype=torch.float64, device=dev)
+    takes = torch.zeros((B, T, K), dtype=torch.bool, device=dev)
+    d = graph.log_start[None, :K] + lp[:, 0]
+    for i in range(1, T):
+        vs = d + graph.log_self[None, :]
+        va = torch.where(has_p[None, :], d[:, p] + adv_p[None, :],
+                         ninf)
+        take = has_p[None, :] & (va > vs)
+        # maximum(vs, va), with the tie going to the self loop
+        d = torch.where(take, va, vs) + lp[:, i]
+        takes[:, i] = take
+    final = d + graph.log_end[None, :K]
+    score = final.max(dim=1).values
+    ks = torch.arange(K, device=dev)
+    s = torch.where(final == score[:, None], ks[None, :],
+                    K).min(dim=1).values                  # lowest k
+    path = torch.empty((B, T), dtype=torch.int64, device=dev)
+    for i in range(T - 1, -1, -1):
+        path[:, i] = s
+        tk = takes[:, i].gather(1, s[:, None])[:, 0]
+        s = torch.where(tk, p[s], s)
+    return path, score
 
 
 class EventSegment:
@@ -258,6 +300,56 @@ class EventSegment:
         ll = torch.logsumexp(alphas[:, T - 1] + graph.log_end[None, :],
                              dim=1)
         return log_gamma[:, :, :K], ll
+
+    def _viterbi_batch(self, logprob):
+        """Batched MAP event path (Viterbi) over the chain graph.
+
+        Parameters
+        ----------
+        logprob : torch [B, T, K] log observation probabilities.
+
+        Returns
+        -------
+        path : torch [B, T] integer event labels (int32 from the kernel,
+            int64 from the torch path).
+        score : torch [B] fp64 joint log-probability of that path.  (The
+            recursion itself gives -inf when no path fits a chain into T
+            steps; the chain graph refuses such a T first, with the
+            "Too few timepoints" error every inference method raises.)
+
+        The max-plus recursion over the sparse chain vectors, in this
+        operation order (fp64 additions and comparisons only, so the
+        kernel and the torch path agree bit for bit)::
+
+            d_0[k]    = log_start[k] + lp[0,k]
+            vs        = d_{t-1}[k] + log_self[k]
+            va        = d_{t-1}[pred[k]] + log_adv[pred[k]]  (-inf at a head)
+            take_t[k] = pred[k] >= 0 and va > vs   (ties keep the self loop)
+            d_t[k]    = (take_t[k] ? va : vs) + lp[t,k]
+            final     = lowest k maximising d_{T-1}[k] + log_end[k]
+            path[T-1] = final
+            path[t-1] = take_t[path[t]] ? pred[path[t]] : path[t]
+
+        Dispatch is that of ``_forward_backward_batch``: one HIP launch
+        (``ops.hmm_viterbi``) for CUDA input with K <= 64, the torch
+        T-loop otherwise and under ``BRAINIAK_EVENTSEG_FB=torch``.
+        """
+        B, T, K = logprob.shape
+        dev = logprob.device
+        graph = self._chain_graph(T, dev)
+        self.p_start, self.p_end, self.P = (graph.p_start.copy(),
+                                            graph.p_end.copy(),
+                                            graph.P.copy())
+        lp = logprob.to(torch.float64)
+
+        if (lp.is_cuda and K <= _HIP_FB_MAX_K
+                and os.environ.get("BRAINIAK_EVENTSEG_FB", "") != "torch"
+                and ops.require_hip()):
+            return ops.hmm_viterbi(
+                lp.contiguous(), graph.log_start, graph.log_end,
+                graph.log_self, graph.log_adv, graph.pred, graph.succ)
+
+        return _viterbi_torch(lp, graph)
 
     def _forward_backward(self, logprob):
         """Single-sequence wrapper; returns (log_gamma [T, K], ll)."""
@@ -516,16 +608,27 @@ class EventSegment:
         (segments, lls): list of [T_r, K] soft segmentations and an
         [n_regions] array of log-likelihoods, in input order.
         """
+        segments = [None] * len(datasets)
+        lls = np.empty(len(datasets))
+        for idxs, lp in self._regions_logprob(models, datasets, var):
+            lg, ll = self._forward_backward_batch(lp)
+            seg = torch.exp(lg).cpu().numpy()
+            ll_h = ll.cpu().numpy()
+            for j, i in enumerate(idxs):
+                segments[i] = seg[j]
+                lls[i] = ll_h[j]
+        return segments, lls
+
+    def _regions_logprob(self, models, datasets, var):
+        """Yield (region indices, logprob [b, T, K]) per (T, V) shape
+        group: region r's data under region r's fitted patterns."""
         if len(models) != len(datasets):
             raise ValueError("models and datasets must pair up")
         dev = torch.device(self.device)
-        K = self.n_events
         groups = {}
         for i, d in enumerate(datasets):
             d2 = _as_valid_2d(d)
             groups.setdefault(d2.shape, []).append(i)
-        segments = [None] * len(datasets)
-        lls = np.empty(len(datasets))
         for (T, V), idxs in groups.items():
             X = torch.stack([
                 torch.as_tensor(np.asarray(datasets[i],
@@ -536,14 +639,35 @@ class EventSegment:
                                            dtype=np.float64),
                                 device=dev) for i in idxs])
             vs = var if var is not None else models[idxs[0]].event_var_
-            lp = self._logprob_obs_batch_perregion(X, pats, vs)
-            lg, ll = self._forward_backward_batch(lp)
-            seg = torch.exp(lg).cpu().numpy()
-            ll_h = ll.cpu().numpy()
+            yield idxs, self._logprob_obs_batch_perregion(X, pats, vs)
+
+    def decode_regions(self, models, datasets, var=None):
+        """Batched counterpart of ``decode`` (and the hard-label twin of
+        ``find_events_regions``): the MAP event path of region r's
+        dataset under region r's fitted model, one Viterbi pass per
+        (T, V) shape group.
+
+        Parameters
+        ----------
+        models : list of fitted EventSegment (e.g. from fit_regions).
+        datasets : list of [T_r, V_r] arrays, same length.
+        var : optional shared variance override.
+
+        Returns
+        -------
+        (events, logps): list of [T_r] int64 label arrays and an
+        [n_regions] array of path log-probabilities, in input order.
+        """
+        events = [None] * len(datasets)
+        logps = np.empty(len(datasets))
+        for idxs, lp in self._regions_logprob(models, datasets, var):
+            path, score = self._viterbi_batch(lp)
+            path_h = path.cpu().numpy().astype(np.int64)
+            score_h = score.cpu().numpy()
             for j, i in enumerate(idxs):
-                segments[i] = seg[j]
-                lls[i] = ll_h[j]
-        return segments, lls
+                events[i] = path_h[j]
+                logps[i] = score_h[j]
+        return events, logps
 
     # -- inference ---------------------------------------------------------
 
@@ -553,9 +677,9 @@ class EventSegment:
                              "number of events")
         self.event_pat_ = event_pat.copy()
 
-    def find_events(self, testing_data, var=None, scramble=False):
-        """Segment a new dataset with the learned event patterns;
-        returns (soft segmentation [T, K], log-likelihood)."""
+    def _inference_var(self, var):
+        """The variance to segment with; raises unless patterns (and a
+        variance, when none is given) have been set."""
         if var is None:
             if not hasattr(self, "event_var_"):
                 raise NotFittedError("Event variance must be provided, if "
@@ -564,6 +688,12 @@ class EventSegment:
         if not hasattr(self, "event_pat_"):
             raise NotFittedError("The event patterns must first be set "
                                  "by fit() or set_event_patterns()")
+        return var
+
+    def find_events(self, testing_data, var=None, scramble=False):
+        """Segment a new dataset with the learned event patterns;
+        returns (soft segmentation [T, K], log-likelihood)."""
+        var = self._inference_var(var)
         if scramble:
             mean_pat = self.event_pat_[:, np.random.permutation(
                 self.n_events)]
@@ -572,6 +702,27 @@ class EventSegment:
         logprob = self._logprob_obs(testing_data.T, mean_pat, var)
         lg, test_ll = self._forward_backward(logprob)
         return np.exp(lg), test_ll
+
+    def decode(self, testing_data, var=None):
+        """Most probable event path (Viterbi / MAP decode) of a new
+        dataset under the learned event patterns.
+
+        Unlike ``predict`` (argmax of the posterior marginals, which can
+        skip events, step backwards or hop between chains) the result is
+        a path of the model: it starts at a chain head, ends at a chain
+        tail and moves by 0 or one event per timepoint.
+
+        Returns (events [T] int64, logp): the labels and the joint
+        log-probability of that path, on the per-voxel scale of
+        ``find_events``'s log-likelihood (so ``logp <= ll``).  Validation
+        is that of ``find_events``, including its "Too few timepoints"
+        error for a T that cannot hold a chain.
+        """
+        var = self._inference_var(var)
+        logprob = self._logprob_obs(testing_data.T, self.event_pat_, var)
+        lp = torch.as_tensor(logprob, device=torch.device(self.device))
+        path, score = self._viterbi_batch(lp[None])
+        return path[0].cpu().numpy().astype(np.int64), float(score[0])
 
     def predict(self, X):
         """Hard event label per timepoint (argmax of find_events)."""

@@ -15,6 +15,8 @@ factoranalysis/tfa_extension.cpp, eventseg/_utils.pyx):
                           (N8/N9)
  - ``hmm_forward_backward`` — single-launch log-space forward-backward
                           over EventSegment's event chains (N10)
+ - ``hmm_viterbi``      — single-launch MAP event path (Viterbi) over
+                          the same chains (N10)
 
 Build: ``python setup.py build_ext --inplace`` (hipcc, gfx950) or
 ``__graft_entry__.build()``.  The extension is REQUIRED whenever CUDA
@@ -40,6 +42,8 @@ __all__ = [
     "has_hip",
     "hmm_fb_tile",
     "hmm_forward_backward",
+    "hmm_viterbi",
+    "hmm_viterbi_tile",
     "isfc_accum_",
     "stencil3d",
     "load_extension",
@@ -223,7 +227,7 @@ def tfa_recon(X: torch.Tensor, W: torch.Tensor, F: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
-# EventSegment forward-backward (N10)
+# EventSegment forward-backward and MAP path (N10)
 # ---------------------------------------------------------------------------
 
 def hmm_forward_backward(logprob: torch.Tensor, log_start: torch.Tensor,
@@ -250,6 +254,34 @@ def hmm_fb_tile() -> int:
     """Timesteps per streamed tile of the forward-backward kernel (the
     sizes around which its tile-tail paths switch)."""
     return int(_ext().hmm_fb_tile())
+
+
+def hmm_viterbi(logprob: torch.Tensor, log_start: torch.Tensor,
+                log_end: torch.Tensor, log_self: torch.Tensor,
+                log_adv: torch.Tensor, pred: torch.Tensor,
+                succ: torch.Tensor):
+    """MAP state path (Viterbi) over left-to-right event chains in one
+    launch; same layout and arguments as ``hmm_forward_backward``.
+
+    Max-plus recursion in fp64 additions and comparisons only: a state
+    advances from ``pred[k]`` only when that is strictly better than its
+    self loop, and the final state is the lowest k at the maximum of
+    ``d[T-1] + log_end``.  Bit-identical to the torch recursion of
+    ``EventSegment._viterbi_batch``.
+
+    Returns (path [B, T] int32, score [B] fp64 joint log-probability of
+    that path; -inf when no path fits a chain into T steps, which only
+    chain vectors built for a longer sequence allow).
+    """
+    path, score = _ext().hmm_viterbi(logprob, log_start, log_end,
+                                     log_self, log_adv, pred, succ)
+    return path, score
+
+
+def hmm_viterbi_tile() -> int:
+    """Timesteps per backtrace tile of the Viterbi kernel (its forward
+    pass streams ``logprob`` in ``hmm_fb_tile()`` steps)."""
+    return int(_ext().hmm_viterbi_tile())
 
 
 # ---------------------------------------------------------------------------

@@ -58,6 +58,10 @@ void launch_hmm_fb(const double*, const double*, const double*,
                    const double*, const double*, const int*, const int*,
                    double*, double*, ll, int, int, void*);
 int hmm_fb_tile(void);
+void launch_hmm_viterbi(const double*, const double*, const double*,
+                        const double*, const double*, const int*, ll*,
+                        int*, double*, ll, int, int, void*);
+int hmm_viterbi_tile(void);
 }
 
 static void* cur_stream() {
@@ -571,15 +575,17 @@ torch::Tensor isfc_accum_(torch::Tensor acc, torch::Tensor M) {
     return acc;
 }
 
-std::vector<torch::Tensor> hmm_forward_backward(
-        torch::Tensor logprob, torch::Tensor log_start,
-        torch::Tensor log_end, torch::Tensor log_self,
-        torch::Tensor log_adv, torch::Tensor pred, torch::Tensor succ) {
-    // single-launch log-space forward-backward over the K event states
-    // of EventSegment's chain graph (hmm_kernels.hip::k_hmm_fb)
+// argument checks shared by the two chain-graph recursions
+static void check_hmm_args(const char* op, const torch::Tensor& logprob,
+                           const torch::Tensor& log_start,
+                           const torch::Tensor& log_end,
+                           const torch::Tensor& log_self,
+                           const torch::Tensor& log_adv,
+                           const torch::Tensor& pred,
+                           const torch::Tensor& succ) {
     check_3d(logprob, torch::kFloat64, "logprob");
     ll B = logprob.size(0), T = logprob.size(1), K = logprob.size(2);
-    TORCH_CHECK(K >= 1 && K <= 64, "hmm_forward_backward needs "
+    TORCH_CHECK(K >= 1 && K <= 64, op, " needs "
                 "1 <= K <= 64 event states (got ", K, ")");
     TORCH_CHECK(T >= 1 && T <= INT_MAX / 64, "T out of range");
     TORCH_CHECK(B <= INT_MAX, "too many sequences for one launch");
@@ -601,6 +607,17 @@ std::vector<torch::Tensor> hmm_forward_backward(
                     && v->device() == logprob.device(),
                     "pred/succ must be contiguous int32 [K] on GPU");
     }
+}
+
+std::vector<torch::Tensor> hmm_forward_backward(
+        torch::Tensor logprob, torch::Tensor log_start,
+        torch::Tensor log_end, torch::Tensor log_self,
+        torch::Tensor log_adv, torch::Tensor pred, torch::Tensor succ) {
+    // single-launch log-space forward-backward over the K event states
+    // of EventSegment's chain graph (hmm_kernels.hip::k_hmm_fb)
+    check_hmm_args("hmm_forward_backward", logprob, log_start, log_end,
+                   log_self, log_adv, pred, succ);
+    ll B = logprob.size(0), T = logprob.size(1), K = logprob.size(2);
     auto log_gamma = torch::empty({B, T, K}, logprob.options());
     auto llik = torch::empty({B}, logprob.options());
     if (B == 0) return {log_gamma, llik};
@@ -613,12 +630,43 @@ std::vector<torch::Tensor> hmm_forward_backward(
     return {log_gamma, llik};
 }
 
+std::vector<torch::Tensor> hmm_viterbi(
+        torch::Tensor logprob, torch::Tensor log_start,
+        torch::Tensor log_end, torch::Tensor log_self,
+        torch::Tensor log_adv, torch::Tensor pred, torch::Tensor succ) {
+    // single-launch MAP path over the same chain graph
+    // (hmm_kernels.hip::k_hmm_viterbi); succ is checked for interface
+    // symmetry, the recursion only walks pred
+    check_hmm_args("hmm_viterbi", logprob, log_start, log_end, log_self,
+                   log_adv, pred, succ);
+    ll B = logprob.size(0), T = logprob.size(1), K = logprob.size(2);
+    auto path = torch::empty({B, T}, logprob.options().dtype(torch::kInt32));
+    auto score = torch::empty({B}, logprob.options());
+    if (B == 0) return {path, score};
+    // one 64-bit back-pointer word per (sequence, timestep)
+    auto masks = torch::empty({B, T},
+                              logprob.options().dtype(torch::kInt64));
+    launch_hmm_viterbi(logprob.data_ptr<double>(),
+                       log_start.data_ptr<double>(),
+                       log_end.data_ptr<double>(),
+                       log_self.data_ptr<double>(),
+                       log_adv.data_ptr<double>(), pred.data_ptr<int>(),
+                       (ll*)masks.data_ptr<int64_t>(), path.data_ptr<int>(),
+                       score.data_ptr<double>(), B, (int)T, (int)K,
+                       cur_stream());
+    return {path, score};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("hmm_forward_backward", &hmm_forward_backward,
           "log-space HMM forward-backward over chain states "
           "-> (log_gamma [B,T,K], ll [B])");
     m.def("hmm_fb_tile", []() { return hmm_fb_tile(); },
           "timesteps per streamed tile of k_hmm_fb");
+    m.def("hmm_viterbi", &hmm_viterbi,
+          "MAP path over chain states -> (path int32 [B,T], score [B])");
+    m.def("hmm_viterbi_tile", []() { return hmm_viterbi_tile(); },
+          "timesteps per backtrace tile of k_hmm_viterbi");
     m.def("stencil3d", &stencil3d,
           "direct [K,K,K] valid conv over [B,X,Y,Z] (searchlight ball)");
     m.def("isfc_accum_", &isfc_accum_,
