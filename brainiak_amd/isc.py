@@ -20,7 +20,13 @@ MI355X additions:
    each rank holds a subset of subjects, the across-subject (nan-aware)
    sum rides ONE all-reduce, and each rank correlates its subjects
    against the leave-one-out mean on its own GPU (BASELINE config 4:
-   50k voxels x 32 subjects over xGMI).
+   50k voxels x 32 subjects over xGMI);
+ - ``bootstrap_isc`` / ``permutation_isc`` / leave-one-out
+   ``timeshift_isc`` take ``device=``: the null distribution is then a
+   per-draw gather + median / Fisher mean over a fixed table
+   (``_resample_stat``: the HIP kernel ``ops.isc_resample_stat`` on a
+   GPU, its torch twin elsewhere) from the same draws as the numpy
+   path.
 
 Citations as in the reference: [Hasson2004], [Simony2016], [Chen2016],
 [HallWilson1991], [PhipsonSmyth2010], [SilverDunlap1987].
@@ -425,15 +431,237 @@ def _coerce_iscs(iscs, pairwise):
     return iscs, n_subjects, iscs.shape[1]
 
 
+# --------------------------------------------------------------------------
+# device path of the resampling nulls
+#
+# Per draw and per voxel, every variant of the bootstrap, sign-flip,
+# label-shuffle and time-shift tests gathers one value per subject (or
+# pair) from a fixed table, optionally flips its sign or leaves it out,
+# and takes the NaN-skipping median or Fisher mean of what it gathered.
+# ``_resample_stat`` is that step: the HIP kernel
+# ``ops.isc_resample_stat`` on a GPU table, a chunked torch twin
+# anywhere else.
+# --------------------------------------------------------------------------
+
+# byte budget of the torch twin's [chunk, R, V] intermediates
+_RESAMPLE_CHUNK_BYTES = 512 << 20
+# live [chunk, R, V]-sized tensors at the twin's peak (gathered values,
+# signed values, sorted values and the sort's int64 indices)
+_RESAMPLE_CHUNK_COPIES = 4
+# byte budget of one voxel chunk of the time-shift lag table with its
+# FFT temporaries
+_TIMESHIFT_CHUNK_BYTES = 2 << 30
+# table-sized tensors alive while a lag table is built (series, LOO
+# means, their unit forms, two half-spectra of complex128, the table)
+_TIMESHIFT_CHUNK_COPIES = 8
+
+
+def _host_tensor(a, name):
+    """Index / sign array (numpy or torch, any device) → int64 tensor
+    on the host."""
+    import torch
+    t = a.detach().cpu() if isinstance(a, torch.Tensor) \
+        else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype.is_floating_point or t.dtype.is_complex \
+            or t.dtype == torch.bool:
+        raise ValueError(f"{name} must be an integer array")
+    return t.to(torch.int64)
+
+
+def _resample_stat_torch(table, rows, lags, signs, stat):
+    """Torch twin of ``ops.isc_resample_stat`` on any device, chunked
+    over draws.  rows / lags / signs are tensors on the table's device;
+    lags may be None."""
+    import torch
+    N, L, V = table.shape
+    n_draws, R = rows.shape
+    out = torch.full((n_draws, V), float("nan"), dtype=torch.float64,
+                     device=table.device)
+    if R == 0 or V == 0:
+        return out
+    flat = table.reshape(N * L, V)
+    index = rows.long() * L
+    if lags is not None:
+        index = index + lags.long()
+    per_draw = R * V * 8 * _RESAMPLE_CHUNK_COPIES
+    chunk = max(1, _RESAMPLE_CHUNK_BYTES // per_draw)
+    nan = torch.tensor(float("nan"), dtype=torch.float64,
+                       device=table.device)
+    for a in range(0, n_draws, chunk):
+        b = min(n_draws, a + chunk)
+        sg = signs[a:b].to(torch.float64)[:, :, None]
+        x = torch.where(sg != 0, flat[index[a:b]] * sg, nan)  # [c, R, V]
+        if stat == 'median':
+            n = (~torch.isnan(x)).sum(dim=1)            # [c, V]
+            # NaNs sort last; numpy's rule for an even count is the
+            # mean of the two middle values (torch.nanmedian takes
+            # the lower one)
+            xs = torch.sort(x, dim=1).values
+            hi = (n // 2).clamp(max=R - 1)
+            lo = ((n - 1) // 2).clamp(min=0)
+            v_hi = torch.gather(xs, 1, hi[:, None, :])[:, 0, :]
+            v_lo = torch.gather(xs, 1, lo[:, None, :])[:, 0, :]
+            med = torch.where(lo == hi, v_hi, (v_lo + v_hi) / 2)
+            out[a:b] = torch.where(n > 0, med, nan)
+        else:
+            z = torch.atanh(x)
+            ok = ~torch.isnan(z)
+            total = torch.where(ok, z, torch.zeros_like(z)).sum(dim=1)
+            out[a:b] = torch.tanh(total / ok.sum(dim=1))
+    return out
+
+
+def _resample_stat(table, rows, lags, signs, stat):
+    """out[i, v] = stat over the r with signs[i, r] != 0 and a non-NaN
+    value of signs[i, r] * table[rows[i, r], lags[i, r], v].
+
+    table : fp64 tensor [N, L, V] on the compute device.
+    rows, lags, signs : integer arrays [I, R] (numpy or torch); lags may
+        be None (all zero); signs hold +1 / -1 / 0 (0 leaves the entry
+        out).  They are range-checked here, on the host, before any
+        upload.
+    stat : 'median' (numpy's nanmedian, even-count rule included) or
+        'mean' (tanh(mean(atanh(x))); atanh results that are NaN are
+        skipped, infinities are not).
+
+    A GPU table goes through the HIP kernel ``ops.isc_resample_stat``
+    (for 'median' while R is within ``ops.isc_resample_max_rows()``);
+    everything else, and everything under
+    ``BRAINIAK_ISC_RESAMPLE=torch``, takes the torch twin.  Returns an
+    fp64 tensor [I, V] on the table's device.
+    """
+    import torch
+    from . import ops
+    if stat not in ('mean', 'median'):
+        raise ValueError("Summary statistic must be 'mean' or 'median'")
+    if not isinstance(table, torch.Tensor) or table.dim() != 3 \
+            or table.dtype != torch.float64:
+        raise ValueError("table must be an fp64 tensor [N, L, V]")
+    N, L, V = table.shape
+    rows_h = _host_tensor(rows, "rows")
+    signs_h = _host_tensor(signs, "signs")
+    lags_h = None if lags is None else _host_tensor(lags, "lags")
+    if rows_h.dim() != 2:
+        raise ValueError("rows must be [I, R]")
+    if signs_h.shape != rows_h.shape or (
+            lags_h is not None and lags_h.shape != rows_h.shape):
+        raise ValueError("rows, lags and signs must have the same shape")
+    if rows_h.numel():
+        if int(rows_h.min()) < 0 or int(rows_h.max()) >= N:
+            raise ValueError(f"rows must lie in [0, {N})")
+        if lags_h is not None and (int(lags_h.min()) < 0
+                                   or int(lags_h.max()) >= L):
+            raise ValueError(f"lags must lie in [0, {L})")
+        if L < 1:
+            raise ValueError("table has no lags to gather from")
+        if int(signs_h.abs().max()) > 1:
+            raise ValueError("signs must be +1, -1 or 0")
+    R = rows_h.shape[1]
+
+    dev = table.device
+    table = table.contiguous()
+    rows_d = rows_h.to(torch.int32).to(dev)
+    signs_d = signs_h.to(torch.int8).to(dev)
+    lags_d = None if lags_h is None else lags_h.to(torch.int32).to(dev)
+
+    if (table.is_cuda
+            and os.environ.get("BRAINIAK_ISC_RESAMPLE", "") != "torch"
+            and ops.require_hip()
+            and (stat == 'mean' or R <= ops.isc_resample_max_rows())):
+        return ops.isc_resample_stat(table, rows_d, lags_d, signs_d, stat)
+    return _resample_stat_torch(table, rows_d, lags_d, signs_d, stat)
+
+
+def _rows_null_device(iscs, rows, signs, summary_statistic, device):
+    """Null distribution [I, voxel] (numpy) of a test whose draws pick
+    rows of the ISC matrix itself (bootstrap, permutation)."""
+    import torch
+    table = torch.from_numpy(
+        np.ascontiguousarray(iscs, dtype=np.float64))[:, None, :]
+    out = _resample_stat(table.to(torch.device(device)), rows, None,
+                         signs, summary_statistic)
+    return out.cpu().numpy()
+
+
+def _bootstrap_null_device(iscs, draws, n_subjects, pairwise,
+                           summary_statistic, device):
+    """Bootstrap null from the sorted subject draws [boot, subject]."""
+    if not pairwise:
+        return _rows_null_device(iscs, draws, np.ones_like(draws),
+                                 summary_statistic, device)
+    # the resampled pair (a, b), a < b, is the condensed pair of
+    # subjects (draws[a], draws[b]); draws are sorted, so the first
+    # is never the larger, and equal ones are left out
+    iu = np.triu_indices(n_subjects, k=1)
+    first, second = draws[:, iu[0]], draws[:, iu[1]]
+    distinct = first != second
+    pair = (first * n_subjects - first * (first + 1) // 2
+            + (second - first - 1))
+    return _rows_null_device(iscs, np.where(distinct, pair, 0),
+                             distinct.astype(np.int8),
+                             summary_statistic, device)
+
+
+def _identity_rows(n_draws, n_rows):
+    return np.broadcast_to(np.arange(n_rows), (n_draws, n_rows))
+
+
+def _timeshift_lag_table(x):
+    """All circular lags of every subject against its leave-one-out
+    mean: x [S, T, V] → C [S, T, V] with C[s, k, v] the correlation of
+    subject s rolled by k with the unshifted mean of the others."""
+    import torch
+    n_subjects, n_TRs, _ = x.shape
+    loo = (x.sum(dim=0, keepdim=True) - x) / (n_subjects - 1)
+
+    def unit(a):
+        a = a - a.mean(dim=1, keepdim=True)
+        return a / a.square().sum(dim=1, keepdim=True).sqrt()
+
+    fx = torch.fft.rfft(unit(x), dim=1)
+    fm = torch.fft.rfft(unit(loo), dim=1)
+    # n_TRs may be odd: the output length has to be given
+    return torch.fft.irfft(fx.conj() * fm, n=n_TRs, dim=1).contiguous()
+
+
+def _timeshift_null_device(data, shifts, summary_statistic, device):
+    """Leave-one-out time-shift null [shift, voxel] (numpy) from the
+    per-draw subject shifts [shift, subject], in voxel chunks."""
+    import torch
+    dev = torch.device(device)
+    n_TRs, n_voxels, n_subjects = data.shape
+    n_shifts = shifts.shape[0]
+    rows = _identity_rows(n_shifts, n_subjects)
+    signs = np.ones((n_shifts, n_subjects), dtype=np.int8)
+    per_voxel = n_subjects * n_TRs * 8 * _TIMESHIFT_CHUNK_COPIES
+    chunk = max(64, _TIMESHIFT_CHUNK_BYTES // per_voxel // 64 * 64)
+    distribution = np.empty((n_shifts, n_voxels))
+    for a in range(0, n_voxels, chunk):
+        b = min(n_voxels, a + chunk)
+        x = torch.from_numpy(data[:, a:b, :]).to(
+            device=dev, dtype=torch.float64)
+        table = _timeshift_lag_table(x.permute(2, 0, 1).contiguous())
+        del x
+        out = _resample_stat(table, rows, shifts, signs,
+                             summary_statistic)
+        distribution[:, a:b] = out.cpu().numpy()
+        del table, out
+    return distribution
+
+
 def bootstrap_isc(iscs, pairwise=False, summary_statistic='median',
                   n_bootstraps=1000, ci_percentile=95, side='right',
-                  random_state=None):
+                  random_state=None, device=None):
     """One-sample subject-level bootstrap with the Hall-Wilson shift.
 
     All ``n_bootstraps`` subject resamples are drawn up front and the
     summary statistic is applied to the whole [boot, subject, voxel]
     stack at once.  Resampled pairs of a subject with itself (pairwise
     mode) carry no information and are excluded as NaN.
+
+    ``device`` (``"cpu"``, ``"cuda"``, a ``torch.device``): compute the
+    bootstrap distribution on that device (``_resample_stat``) from the
+    same draws; ``None`` keeps the numpy path.
     """
     iscs, n_subjects, n_voxels = _coerce_iscs(iscs, pairwise)
     if summary_statistic not in ('mean', 'median'):
@@ -445,7 +673,10 @@ def bootstrap_isc(iscs, pairwise=False, summary_statistic='median',
     draws = np.sort(rng.randint(0, n_subjects,
                                 size=(n_bootstraps, n_subjects)), axis=1)
 
-    if pairwise:
+    if device is not None:
+        distribution = _bootstrap_null_device(
+            iscs, draws, n_subjects, pairwise, summary_statistic, device)
+    elif pairwise:
         # square per-voxel matrices once, then each bootstrap is a
         # row/column gather + upper-triangle read
         V = n_voxels
@@ -461,8 +692,9 @@ def bootstrap_isc(iscs, pairwise=False, summary_statistic='median',
     else:
         samples = iscs[draws]                   # [boot, subject, voxel]
 
-    distribution = compute_summary_statistic(
-        samples, summary_statistic=summary_statistic, axis=1)
+    if device is None:
+        distribution = compute_summary_statistic(
+            samples, summary_statistic=summary_statistic, axis=1)
 
     half_alpha = (100 - ci_percentile) / 2
     ci = (np.percentile(distribution, half_alpha, axis=0),
@@ -544,10 +776,14 @@ def _sign_flip_rows(layout, flips, pairwise):
 
 def permutation_isc(iscs, group_assignment=None, pairwise=False,
                     summary_statistic='median', n_permutations=1000,
-                    side='right', random_state=None):
+                    side='right', random_state=None, device=None):
     """One-sample (sign-flip) / two-sample (label-shuffle) permutation
     test; exact enumeration when the permutation space fits in
-    n_permutations."""
+    n_permutations.
+
+    ``device`` (``"cpu"``, ``"cuda"``, a ``torch.device``): compute the
+    permutation distribution on that device (``_resample_stat``) from
+    the same flips / label orders; ``None`` keeps the numpy path."""
     iscs, n_subjects, n_voxels = _coerce_iscs(iscs, pairwise)
     if summary_statistic not in ('mean', 'median'):
         raise ValueError("Summary statistic must be 'mean' or 'median'")
@@ -572,10 +808,15 @@ def permutation_isc(iscs, group_assignment=None, pairwise=False,
             flips = rng.choice([-1.0, 1.0],
                                size=(n_permutations, n_subjects))
         row_signs = _sign_flip_rows(layout, flips, pairwise)
-        # [perm, row, voxel] in one broadcast multiply
-        flipped = iscs[None] * row_signs[:, :, None]
-        distribution = compute_summary_statistic(
-            flipped, summary_statistic=summary_statistic, axis=1)
+        if device is not None:
+            distribution = _rows_null_device(
+                iscs, _identity_rows(*row_signs.shape),
+                row_signs.astype(np.int8), summary_statistic, device)
+        else:
+            # [perm, row, voxel] in one broadcast multiply
+            flipped = iscs[None] * row_signs[:, :, None]
+            distribution = compute_summary_statistic(
+                flipped, summary_statistic=summary_statistic, axis=1)
     else:
         observed = np.array(_group_difference(
             iscs, layout.selector, layout.labels, summary_statistic))
@@ -587,15 +828,32 @@ def permutation_isc(iscs, group_assignment=None, pairwise=False,
                       for _ in range(n_permutations)]
         rows = []
         base = np.asarray(layout.assignment)
-        for order in orders:
+        if device is not None:
+            # the selector of every permutation at once: a row belongs
+            # to a group's call where its (shuffled) label is that
+            # group's; cross-group pairs (NaN labels) belong to neither
+            orders = np.asarray(orders)
             if pairwise:
-                shuffled_matrix = layout.matrix[np.ix_(order, order)]
-                selector = squareform(shuffled_matrix, checks=False)
+                iu = np.triu_indices(n_subjects, k=1)
+                selectors = layout.matrix[orders[:, iu[0]],
+                                          orders[:, iu[1]]]
             else:
-                selector = base[np.asarray(order)]
-            rows.append(_group_difference(
-                iscs, selector, layout.labels, summary_statistic))
-        distribution = np.array(rows)
+                selectors = base[orders]
+            groups = [_rows_null_device(
+                iscs, _identity_rows(*selectors.shape),
+                (selectors == label).astype(np.int8),
+                summary_statistic, device) for label in layout.labels]
+            distribution = groups[0] - groups[1]
+        else:
+            for order in orders:
+                if pairwise:
+                    shuffled_matrix = layout.matrix[np.ix_(order, order)]
+                    selector = squareform(shuffled_matrix, checks=False)
+                else:
+                    selector = base[np.asarray(order)]
+                rows.append(_group_difference(
+                    iscs, selector, layout.labels, summary_statistic))
+            distribution = np.array(rows)
 
     p = p_from_null(observed, distribution, side=side, exact=exact,
                     axis=0)
@@ -629,13 +887,36 @@ def _loo_null_isc(surrogate, data, summary_statistic, tolerate_nans):
 
 def timeshift_isc(data, pairwise=False, summary_statistic='median',
                   n_shifts=1000, side='right', tolerate_nans=True,
-                  random_state=None):
-    """Circular time-shift null distribution for a one-sample ISC test."""
+                  random_state=None, device=None):
+    """Circular time-shift null distribution for a one-sample ISC test.
+
+    ``device`` (``"cpu"``, ``"cuda"``, a ``torch.device``): compute the
+    null distribution on that device from the same shifts; ``None``
+    keeps the numpy path.  Rolling subject s by k and correlating it
+    with the unshifted leave-one-out mean is their circular
+    cross-correlation at lag k, so all lags are tabulated once (by FFT,
+    in voxel chunks) and every draw is a lookup (``_resample_stat``).
+    Leave-one-out only: the pair-lag tables of the pairwise test would
+    be n_subjects^2 / 2 times the data.
+    """
+    if device is not None and pairwise:
+        raise ValueError("timeshift_isc: the device path is "
+                         "leave-one-out only; use device=None with "
+                         "pairwise=True")
     data, n_TRs, n_voxels, n_subjects = _check_timeseries_input(data)
     observed = isc(data, pairwise=pairwise,
                    summary_statistic=summary_statistic,
                    tolerate_nans=tolerate_nans)
     rng = _as_rng(random_state)
+
+    if device is not None:
+        # one call draws what the numpy path's per-draw calls draw
+        shifts = rng.randint(0, n_TRs, size=(n_shifts, n_subjects))
+        distribution = _timeshift_null_device(
+            data, shifts, summary_statistic, device)
+        p = p_from_null(observed, distribution, side=side, exact=False,
+                        axis=0)
+        return observed, p, distribution
 
     def one_draw(_):
         shifts = rng.randint(0, n_TRs, size=n_subjects)

@@ -17,6 +17,10 @@ factoranalysis/tfa_extension.cpp, eventseg/_utils.pyx):
                           over EventSegment's event chains (N10)
  - ``hmm_viterbi``      — single-launch MAP event path (Viterbi) over
                           the same chains (N10)
+ - ``isc_resample_stat`` — per-draw gather + NaN-skipping median /
+                          Fisher mean: the null distributions of the
+                          ISC bootstrap, permutation and time-shift
+                          tests
 
 Build: ``python setup.py build_ext --inplace`` (hipcc, gfx950) or
 ``__graft_entry__.build()``.  The extension is REQUIRED whenever CUDA
@@ -44,6 +48,8 @@ __all__ = [
     "hmm_forward_backward",
     "hmm_viterbi",
     "hmm_viterbi_tile",
+    "isc_resample_max_rows",
+    "isc_resample_stat",
     "isfc_accum_",
     "stencil3d",
     "load_extension",
@@ -282,6 +288,37 @@ def hmm_viterbi_tile() -> int:
     """Timesteps per backtrace tile of the Viterbi kernel (its forward
     pass streams ``logprob`` in ``hmm_fb_tile()`` steps)."""
     return int(_ext().hmm_viterbi_tile())
+
+
+# ---------------------------------------------------------------------------
+# ISC resampling statistics
+# ---------------------------------------------------------------------------
+
+def isc_resample_stat(table: torch.Tensor, rows: torch.Tensor, lags,
+                      signs: torch.Tensor, stat: str) -> torch.Tensor:
+    """Per-draw gather and summary statistic in one launch (one lane per
+    voxel, one wave per 64 voxels of a draw).
+
+    table fp64 [N, L, V] contiguous; rows int32 [I, R] into N; lags
+    int32 [I, R] into L or None (all zero); signs int8 [I, R]: +1 / -1
+    multiply the value, 0 leaves the entry out; all on the GPU.  The
+    index ranges are NOT checked here (``isc._resample_stat`` checks
+    them on the host).
+
+    out[i, v] = stat over the r with signs[i, r] != 0 and a non-NaN
+    signs[i, r] * table[rows[i, r], lags[i, r], v]: 'median' is numpy's
+    nanmedian, 'mean' is tanh(mean(atanh(x))); NaN when nothing
+    survives.  'median' needs R <= ``isc_resample_max_rows()``.
+
+    Returns out [I, V] fp64.
+    """
+    return _ext().isc_resample_stat(table, rows, lags, signs, str(stat))
+
+
+def isc_resample_max_rows() -> int:
+    """Largest R the 'median' path of ``isc_resample_stat`` takes (its
+    per-lane sorted column lives in LDS)."""
+    return int(_ext().isc_resample_max_rows())
 
 
 # ---------------------------------------------------------------------------

@@ -1,10 +1,10 @@
 // Torch bindings for the brainiak_amd HIP/CDNA4 kernels (gfx950).
 //
 // The device code lives in fcma_kernels.hip / procrustes.hip /
-// tfa_kernels.hip / hmm_kernels.hip (hand-written HIP, MFMA/LDS — no
-// library GEMMs on the FCMA path); this file validates tensors,
-// allocates outputs, and calls the extern "C" launchers on the current
-// stream.
+// tfa_kernels.hip / hmm_kernels.hip / isc_stats_kernels.hip (hand-written
+// HIP, MFMA/LDS — no library GEMMs on the FCMA path); this file validates
+// tensors, allocates outputs, and calls the extern "C" launchers on the
+// current stream.
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -62,6 +62,10 @@ void launch_hmm_viterbi(const double*, const double*, const double*,
                         const double*, const double*, const int*, ll*,
                         int*, double*, ll, int, int, void*);
 int hmm_viterbi_tile(void);
+void launch_isc_resample_stat(const double*, const int*, const int*,
+                              const signed char*, double*, ll, ll, ll, int,
+                              int, void*);
+int isc_resample_max_rows(void);
 }
 
 static void* cur_stream() {
@@ -657,7 +661,73 @@ std::vector<torch::Tensor> hmm_viterbi(
     return {path, score};
 }
 
+// argument checks of the ISC resampling gather (index ranges are the
+// Python caller's job: the indices are born on the host)
+static void check_isc_resample_args(const torch::Tensor& table,
+                                    const torch::Tensor& rows,
+                                    const c10::optional<torch::Tensor>& lags,
+                                    const torch::Tensor& signs,
+                                    bool median) {
+    check_3d(table, torch::kFloat64, "table");
+    TORCH_CHECK(rows.is_cuda() && rows.is_contiguous() && rows.dim() == 2
+                && rows.scalar_type() == torch::kInt32
+                && rows.device() == table.device(),
+                "rows must be contiguous int32 [I,R] on the table's GPU");
+    TORCH_CHECK(signs.is_cuda() && signs.is_contiguous()
+                && signs.scalar_type() == torch::kInt8
+                && signs.device() == table.device()
+                && signs.sizes() == rows.sizes(),
+                "signs must be contiguous int8 [I,R] on the table's GPU");
+    if (lags.has_value()) {
+        const auto& lg = lags.value();
+        TORCH_CHECK(lg.is_cuda() && lg.is_contiguous()
+                    && lg.scalar_type() == torch::kInt32
+                    && lg.device() == table.device()
+                    && lg.sizes() == rows.sizes(),
+                    "lags must be contiguous int32 [I,R] on the table's "
+                    "GPU (or None)");
+    }
+    ll I = rows.size(0), R = rows.size(1), V = table.size(2);
+    TORCH_CHECK(R <= INT_MAX, "too many rows per draw");
+    TORCH_CHECK(!median || R <= isc_resample_max_rows(),
+                "isc_resample_stat 'median' needs R <= ",
+                isc_resample_max_rows(), " rows per draw (got ", R, ")");
+    TORCH_CHECK(R == 0 || (table.size(0) >= 1 && table.size(1) >= 1),
+                "table has no rows to gather from");
+    TORCH_CHECK(I * ((V + 63) / 64) <= (ll)INT_MAX,
+                "too many (draw, voxel tile) blocks for one launch");
+}
+
+torch::Tensor isc_resample_stat(torch::Tensor table, torch::Tensor rows,
+                                c10::optional<torch::Tensor> lags,
+                                torch::Tensor signs, std::string stat) {
+    // per-draw gather + nan-skipping median / Fisher mean
+    // (isc_stats_kernels.hip::k_isc_resample_stat)
+    TORCH_CHECK(stat == "median" || stat == "mean",
+                "stat must be 'median' or 'mean'");
+    const bool median = stat == "median";
+    check_isc_resample_args(table, rows, lags, signs, median);
+    ll I = rows.size(0), R = rows.size(1);
+    ll L = table.size(1), V = table.size(2);
+    auto out = torch::empty({I, V}, table.options());
+    if (I == 0 || V == 0) return out;
+    launch_isc_resample_stat(
+        table.data_ptr<double>(), rows.data_ptr<int>(),
+        lags.has_value() ? lags.value().data_ptr<int>() : nullptr,
+        (const signed char*)signs.data_ptr<int8_t>(),
+        out.data_ptr<double>(), I, L, V, (int)R, median ? 1 : 0,
+        cur_stream());
+    return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("isc_resample_stat", &isc_resample_stat,
+          "per-draw gather + nanmedian / Fisher mean -> out [I,V] fp64",
+          pybind11::arg("table"), pybind11::arg("rows"),
+          pybind11::arg("lags").none(true), pybind11::arg("signs"),
+          pybind11::arg("stat"));
+    m.def("isc_resample_max_rows", []() { return isc_resample_max_rows(); },
+          "row cap of the median path of k_isc_resample_stat");
     m.def("hmm_forward_backward", &hmm_forward_backward,
           "log-space HMM forward-backward over chain states "
           "-> (log_gamma [B,T,K], ll [B])");
