@@ -26,7 +26,14 @@ MI355X additions:
    per-draw gather + median / Fisher mean over a fixed table
    (``_resample_stat``: the HIP kernel ``ops.isc_resample_stat`` on a
    GPU, its torch twin elsewhere) from the same draws as the numpy
-   path.
+   path;
+ - ``phaseshift_isc`` takes ``device=`` too (leave-one-out and
+   pairwise): the correlation of a phase-randomised series with a fixed
+   one is linear in the cosines and sines of the drawn phases, so the
+   null is one contraction of a per-draw coefficient block with a fixed
+   spectral table followed by the same statistic (``_phase_stat``: the
+   HIP kernel ``ops.isc_phase_stat`` on a GPU, a batched-matmul twin
+   elsewhere), without any per-draw FFT.
 
 Citations as in the reference: [Hasson2004], [Simony2016], [Chen2016],
 [HallWilson1991], [PhipsonSmyth2010], [SilverDunlap1987].
@@ -454,6 +461,13 @@ _TIMESHIFT_CHUNK_BYTES = 2 << 30
 # table-sized tensors alive while a lag table is built (series, LOO
 # means, their unit forms, two half-spectra of complex128, the table)
 _TIMESHIFT_CHUNK_COPIES = 8
+# byte budget of one voxel chunk of the phase-shift table with its FFT
+# temporaries
+_PHASESHIFT_CHUNK_BYTES = 2 << 30
+# table-sized tensors alive while a phase table is built (series, LOO
+# means, their unit forms, two half-spectra of complex128 or the pair
+# products, the table)
+_PHASESHIFT_CHUNK_COPIES = 8
 
 
 def _host_tensor(a, name):
@@ -466,6 +480,30 @@ def _host_tensor(a, name):
             or t.dtype == torch.bool:
         raise ValueError(f"{name} must be an integer array")
     return t.to(torch.int64)
+
+
+def _stat_over_rows(x, stat):
+    """NaN-skipping median (numpy's nanmedian) or Fisher mean over dim 1
+    of x [c, R, V] -> [c, V]; NaN where nothing survives."""
+    import torch
+    R = x.shape[1]
+    nan = torch.tensor(float("nan"), dtype=torch.float64, device=x.device)
+    if stat == 'median':
+        n = (~torch.isnan(x)).sum(dim=1)            # [c, V]
+        # NaNs sort last; numpy's rule for an even count is the
+        # mean of the two middle values (torch.nanmedian takes
+        # the lower one)
+        xs = torch.sort(x, dim=1).values
+        hi = (n // 2).clamp(max=R - 1)
+        lo = ((n - 1) // 2).clamp(min=0)
+        v_hi = torch.gather(xs, 1, hi[:, None, :])[:, 0, :]
+        v_lo = torch.gather(xs, 1, lo[:, None, :])[:, 0, :]
+        med = torch.where(lo == hi, v_hi, (v_lo + v_hi) / 2)
+        return torch.where(n > 0, med, nan)
+    z = torch.atanh(x)
+    ok = ~torch.isnan(z)
+    total = torch.where(ok, z, torch.zeros_like(z)).sum(dim=1)
+    return torch.tanh(total / ok.sum(dim=1))
 
 
 def _resample_stat_torch(table, rows, lags, signs, stat):
@@ -491,23 +529,7 @@ def _resample_stat_torch(table, rows, lags, signs, stat):
         b = min(n_draws, a + chunk)
         sg = signs[a:b].to(torch.float64)[:, :, None]
         x = torch.where(sg != 0, flat[index[a:b]] * sg, nan)  # [c, R, V]
-        if stat == 'median':
-            n = (~torch.isnan(x)).sum(dim=1)            # [c, V]
-            # NaNs sort last; numpy's rule for an even count is the
-            # mean of the two middle values (torch.nanmedian takes
-            # the lower one)
-            xs = torch.sort(x, dim=1).values
-            hi = (n // 2).clamp(max=R - 1)
-            lo = ((n - 1) // 2).clamp(min=0)
-            v_hi = torch.gather(xs, 1, hi[:, None, :])[:, 0, :]
-            v_lo = torch.gather(xs, 1, lo[:, None, :])[:, 0, :]
-            med = torch.where(lo == hi, v_hi, (v_lo + v_hi) / 2)
-            out[a:b] = torch.where(n > 0, med, nan)
-        else:
-            z = torch.atanh(x)
-            ok = ~torch.isnan(z)
-            total = torch.where(ok, z, torch.zeros_like(z)).sum(dim=1)
-            out[a:b] = torch.tanh(total / ok.sum(dim=1))
+        out[a:b] = _stat_over_rows(x, stat)
     return out
 
 
@@ -644,6 +666,167 @@ def _timeshift_null_device(data, shifts, summary_statistic, device):
         del x
         out = _resample_stat(table, rows, shifts, signs,
                              summary_statistic)
+        distribution[:, a:b] = out.cpu().numpy()
+        del table, out
+    return distribution
+
+
+# --------------------------------------------------------------------------
+# device path of the phase-randomisation null
+#
+# Phase randomisation multiplies bin f of a subject's spectrum by
+# exp(i phi_f) (and the mirrored bin by its conjugate); it changes neither
+# the mean nor the norm of the series.  With u the centred unit-norm
+# series, w the centred unit-norm fixed series it is correlated with,
+# U = rfft(u), W = rfft(w) and P = U conj(W), Parseval gives
+#
+#   r = sum_{f=1..F} (2/T) Re P_f cos phi_f - (2/T) Im P_f sin phi_f
+#       + (1/T) Re P_{T/2}                    (even T: the Nyquist bin)
+#
+# with F = (T - 1) // 2 randomised bins and a zero DC term.  The pairwise
+# test has P = U_a conj(U_b) and the phase difference phi_a - phi_b.  So
+# a null value is the dot product of a fixed table column with the
+# cosines and sines of the draw.
+# --------------------------------------------------------------------------
+
+def _phase_tables(x, pairwise):
+    """Spectral table of the phase-shift null: x [S, T, V] -> fp64
+    [R, K, V].  Rows: subjects against their unshifted leave-one-out
+    mean (R = S), or subject pairs in ``combinations`` order (R =
+    S (S - 1) / 2).  Columns: (2/T) Re P_f for f = 1..F, then
+    -(2/T) Im P_f for f = 1..F, then (1/T) Re P_{T/2} for even T, so
+    K = 2 F (+ 1).  All signs and factors of the formula live here; the
+    coefficients are plain cosines, sines and ones."""
+    import torch
+    n_subjects, n_TRs, _ = x.shape
+    F = (n_TRs - 1) // 2
+
+    def unit(a):
+        a = a - a.mean(dim=1, keepdim=True)
+        return a / a.square().sum(dim=1, keepdim=True).sqrt()
+
+    fx = torch.fft.rfft(unit(x), dim=1)                 # [S, T//2+1, V]
+    if pairwise:
+        iu = torch.triu_indices(n_subjects, n_subjects, offset=1,
+                                device=x.device)
+        P = fx[iu[0]] * fx[iu[1]].conj()
+    else:
+        loo = (x.sum(dim=0, keepdim=True) - x) / (n_subjects - 1)
+        P = fx * torch.fft.rfft(unit(loo), dim=1).conj()
+    parts = [P.real[:, 1:F + 1] * (2.0 / n_TRs),
+             P.imag[:, 1:F + 1] * (-2.0 / n_TRs)]
+    if n_TRs % 2 == 0:
+        half = n_TRs // 2
+        parts.append(P.real[:, half:half + 1] * (1.0 / n_TRs))
+    return torch.cat(parts, dim=1).contiguous()
+
+
+def _phase_coef(phases, pairwise, n_TRs):
+    """Coefficient block of the phase-shift null: phases [I, F, S]
+    (radians, a tensor on the compute device) -> fp64 [I, R, K] matching
+    ``_phase_tables``: cos, then sin, of each row's phase (a subject's,
+    or the difference first - second of a pair's), then a column of ones
+    for the Nyquist row of an even ``n_TRs``."""
+    import torch
+    n_draws, _, n_subjects = phases.shape
+    ph = phases.permute(0, 2, 1)                        # [I, S, F]
+    if pairwise:
+        iu = torch.triu_indices(n_subjects, n_subjects, offset=1,
+                                device=phases.device)
+        ph = ph[:, iu[0]] - ph[:, iu[1]]
+    parts = [torch.cos(ph), torch.sin(ph)]
+    if n_TRs % 2 == 0:
+        parts.append(torch.ones((n_draws, ph.shape[1], 1),
+                                dtype=ph.dtype, device=ph.device))
+    return torch.cat(parts, dim=2).contiguous()
+
+
+def _phase_stat_torch(table, coef, stat):
+    """Torch twin of ``ops.isc_phase_stat`` on any device: a batched
+    matmul over the rows, chunked over draws by the byte budget of the
+    resampling twin, then the same statistic."""
+    import torch
+    R, K, V = table.shape
+    n_draws = coef.shape[0]
+    out = torch.full((n_draws, V), float("nan"), dtype=torch.float64,
+                     device=table.device)
+    if V == 0:
+        return out
+    per_draw = R * V * 8 * _RESAMPLE_CHUNK_COPIES
+    chunk = max(1, _RESAMPLE_CHUNK_BYTES // per_draw)
+    for a in range(0, n_draws, chunk):
+        b = min(n_draws, a + chunk)
+        # [R, c, K] @ [R, K, V] -> [R, c, V]
+        x = torch.bmm(coef[a:b].transpose(0, 1), table)
+        out[a:b] = _stat_over_rows(x.transpose(0, 1), stat)
+    return out
+
+
+def _phase_stat(table, coef, stat):
+    """out[i, v] = stat over the r with a non-NaN
+    x[i, r, v] = sum_k coef[i, r, k] * table[r, k, v].
+
+    table : fp64 tensor [R, K, V]; coef : fp64 tensor [I, R, K] on the
+    same device; R >= 1, K >= 1.
+    stat : 'median' or 'mean', as in ``_resample_stat``.
+
+    A GPU table goes through the HIP kernel ``ops.isc_phase_stat`` (for
+    'median' while R is within ``ops.isc_phase_max_rows()``); everything
+    else, and everything under ``BRAINIAK_ISC_RESAMPLE=torch``, takes
+    the torch twin.  Returns an fp64 tensor [I, V] on the table's
+    device.
+    """
+    import torch
+    from . import ops
+    if stat not in ('mean', 'median'):
+        raise ValueError("Summary statistic must be 'mean' or 'median'")
+    for t, name, dims in ((table, "table", "[R, K, V]"),
+                          (coef, "coef", "[I, R, K]")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 \
+                or t.dtype != torch.float64:
+            raise ValueError(f"{name} must be an fp64 tensor {dims}")
+    R, K, _ = table.shape
+    if coef.shape[1:] != (R, K) or coef.device != table.device:
+        raise ValueError("coef [I, R, K] must agree with table [R, K, V] "
+                         "in R and K and share its device")
+    if R < 1 or K < 1:
+        raise ValueError("table needs at least one row and one column")
+    table = table.contiguous()
+    coef = coef.contiguous()
+    if (table.is_cuda
+            and os.environ.get("BRAINIAK_ISC_RESAMPLE", "") != "torch"
+            and ops.require_hip()
+            and (stat == 'mean' or R <= ops.isc_phase_max_rows())):
+        return ops.isc_phase_stat(table, coef, stat)
+    return _phase_stat_torch(table, coef, stat)
+
+
+def _phaseshift_null_device(data, phases, pairwise, summary_statistic,
+                            device):
+    """Phase-shift null [shift, voxel] (numpy) from the drawn phases
+    [shift, F, subject] (radians), in voxel chunks sized by the rows of
+    the table (subjects, or pairs).  The coefficient block is built once,
+    so every chunk sees the same draws."""
+    import torch
+    dev = torch.device(device)
+    n_TRs, n_voxels, n_subjects = data.shape
+    n_shifts = phases.shape[0]
+    n_rows = n_subjects * (n_subjects - 1) // 2 if pairwise \
+        else n_subjects
+    coef = _phase_coef(
+        torch.from_numpy(np.ascontiguousarray(phases, dtype=np.float64))
+        .to(dev), pairwise, n_TRs)
+    per_voxel = max(n_rows, n_subjects) * n_TRs * 8 \
+        * _PHASESHIFT_CHUNK_COPIES
+    chunk = max(64, _PHASESHIFT_CHUNK_BYTES // per_voxel // 64 * 64)
+    distribution = np.empty((n_shifts, n_voxels))
+    for a in range(0, n_voxels, chunk):
+        b = min(n_voxels, a + chunk)
+        x = torch.from_numpy(data[:, a:b, :]).to(
+            device=dev, dtype=torch.float64)
+        table = _phase_tables(x.permute(2, 0, 1).contiguous(), pairwise)
+        del x
+        out = _phase_stat(table, coef, summary_statistic)
         distribution[:, a:b] = out.cpu().numpy()
         del table, out
     return distribution
@@ -934,13 +1117,54 @@ def timeshift_isc(data, pairwise=False, summary_statistic='median',
 
 def phaseshift_isc(data, pairwise=False, summary_statistic='median',
                    n_shifts=1000, side='right', tolerate_nans=True,
-                   random_state=None):
-    """FFT phase-randomization null distribution for an ISC test."""
+                   random_state=None, device=None):
+    """FFT phase-randomization null distribution for an ISC test.
+
+    ``device`` (``"cpu"``, ``"cuda"``, a ``torch.device``): compute the
+    null distribution on that device from the same phase draws;
+    ``None`` keeps the numpy path.  A phase-randomised subject keeps its
+    mean and norm, so its correlation with a fixed series is linear in
+    the cosines and sines of the drawn phases: the spectra are tabulated
+    once (in voxel chunks) and every draw is a dot product with that
+    table (``_phase_stat``), without a per-draw FFT.  Both leave-one-out
+    and ``pairwise=True`` are supported; the observed statistic still
+    comes from ``isc``.
+
+    On the device path ``tolerate_nans`` acts as on the numpy path: with
+    ``pairwise=True`` the voxels that its threshold drops are NaN in the
+    distribution; for leave-one-out it cannot change the null, because a
+    NaN in any subject makes every (plain) leave-one-out mean of that
+    voxel NaN on either path.  A voxel that is constant in some subject
+    is NaN on the device path (its unit-norm series is 0 / 0), where the
+    numpy path correlates the rounding noise that the FFT round trip
+    leaves in the surrogate.
+    """
     data, n_TRs, n_voxels, n_subjects = _check_timeseries_input(data)
     observed = isc(data, pairwise=pairwise,
                    summary_statistic=summary_statistic,
                    tolerate_nans=tolerate_nans)
     rng = _as_rng(random_state)
+
+    if device is not None:
+        if summary_statistic not in ('mean', 'median'):
+            raise ValueError("Summary statistic must be 'mean' or "
+                             "'median'")
+        if n_TRs < 2 or n_subjects < 2:
+            raise ValueError("phaseshift_isc: the device path needs at "
+                             "least 2 TRs and 2 subjects")
+        # one call draws what the numpy path's per-draw
+        # rand(F, 1, n_subjects) calls draw
+        n_freq = (n_TRs - 1) // 2
+        phases = rng.rand(n_shifts, n_freq, 1, n_subjects)[:, :, 0, :] \
+            * 2 * np.pi
+        distribution = _phaseshift_null_device(
+            data, phases, pairwise, summary_statistic, device)
+        if pairwise:
+            _, keep = _drop_bad_voxels(data, tolerate_nans)
+            distribution[:, ~keep] = np.nan
+        p = p_from_null(observed, distribution, side=side, exact=False,
+                        axis=0)
+        return observed, p, distribution
 
     def one_draw(_):
         surrogate = phase_randomize(data, random_state=rng)

@@ -21,6 +21,10 @@ factoranalysis/tfa_extension.cpp, eventseg/_utils.pyx):
                           Fisher mean: the null distributions of the
                           ISC bootstrap, permutation and time-shift
                           tests
+ - ``isc_phase_stat``   — per-draw contraction of a cos/sin coefficient
+                          block with a fixed spectral table + the same
+                          median / Fisher mean: the null distribution of
+                          the ISC phase-randomisation test
 
 Build: ``python setup.py build_ext --inplace`` (hipcc, gfx950) or
 ``__graft_entry__.build()``.  The extension is REQUIRED whenever CUDA
@@ -48,6 +52,8 @@ __all__ = [
     "hmm_forward_backward",
     "hmm_viterbi",
     "hmm_viterbi_tile",
+    "isc_phase_max_rows",
+    "isc_phase_stat",
     "isc_resample_max_rows",
     "isc_resample_stat",
     "isfc_accum_",
@@ -319,6 +325,33 @@ def isc_resample_max_rows() -> int:
     """Largest R the 'median' path of ``isc_resample_stat`` takes (its
     per-lane sorted column lives in LDS)."""
     return int(_ext().isc_resample_max_rows())
+
+
+def isc_phase_stat(table: torch.Tensor, coef: torch.Tensor,
+                   stat: str) -> torch.Tensor:
+    """Contraction and summary statistic of the phase-randomisation null
+    in one launch (one lane per voxel, one wave per 64 voxels of a small
+    tile of draws); the [I, R, V] intermediate stays in registers.
+
+    table fp64 [R, K, V] contiguous; coef fp64 [I, R, K] contiguous;
+    both on the same GPU, R >= 1, K >= 1.
+
+    x[i, r, v] = sum_k coef[i, r, k] * table[r, k, v], and out[i, v] is
+    the statistic over the r with a non-NaN x: 'median' is numpy's
+    nanmedian, 'mean' is tanh(mean(atanh(x))) with NaN atanh results
+    skipped and infinities kept; NaN when nothing survives.  A NaN in
+    the table reaches x through the product.  'median' needs
+    R <= ``isc_phase_max_rows()``.
+
+    Returns out [I, V] fp64.
+    """
+    return _ext().isc_phase_stat(table, coef, str(stat))
+
+
+def isc_phase_max_rows() -> int:
+    """Largest R the 'median' path of ``isc_phase_stat`` takes (its
+    per-lane sorted columns live in LDS)."""
+    return int(_ext().isc_phase_max_rows())
 
 
 # ---------------------------------------------------------------------------

@@ -66,6 +66,10 @@ void launch_isc_resample_stat(const double*, const int*, const int*,
                               const signed char*, double*, ll, ll, ll, int,
                               int, void*);
 int isc_resample_max_rows(void);
+void launch_isc_phase_stat(const double*, const double*, double*, ll, ll,
+                           int, int, int, void*);
+int isc_phase_max_rows(void);
+ll isc_phase_blocks(ll, ll, int, int);
 }
 
 static void* cur_stream() {
@@ -720,7 +724,49 @@ torch::Tensor isc_resample_stat(torch::Tensor table, torch::Tensor rows,
     return out;
 }
 
+torch::Tensor isc_phase_stat(torch::Tensor table, torch::Tensor coef,
+                             std::string stat) {
+    // x[i,r,v] = sum_k coef[i,r,k] * table[r,k,v], then the nan-skipping
+    // median / Fisher mean over r (isc_stats_kernels.hip::k_isc_phase_stat)
+    TORCH_CHECK(stat == "median" || stat == "mean",
+                "stat must be 'median' or 'mean'");
+    const bool median = stat == "median";
+    check_3d(table, torch::kFloat64, "table");
+    TORCH_CHECK(coef.is_cuda() && coef.is_contiguous() && coef.dim() == 3
+                && coef.scalar_type() == torch::kFloat64
+                && coef.device() == table.device(),
+                "coef must be contiguous fp64 [I,R,K] on the table's GPU");
+    ll R = table.size(0), K = table.size(1), V = table.size(2);
+    ll I = coef.size(0);
+    TORCH_CHECK(coef.size(1) == R && coef.size(2) == K,
+                "coef [I,R,K] must agree with table [R,K,V] in R and K");
+    TORCH_CHECK(R >= 1 && K >= 1, "table needs at least one row and one "
+                "column");
+    TORCH_CHECK(!median || R <= isc_phase_max_rows(),
+                "isc_phase_stat 'median' needs R <= ", isc_phase_max_rows(),
+                " rows (got ", R, ")");
+    // segment and voxel indices are 32-bit factors of a 64-bit offset
+    TORCH_CHECK(R * K <= (ll)INT_MAX / 2, "too many table segments (R * K)");
+    TORCH_CHECK(V <= (ll)INT_MAX, "too many voxels for one launch");
+    auto out = torch::empty({I, V}, table.options());
+    if (I == 0 || V == 0) return out;
+    TORCH_CHECK(isc_phase_blocks(I, V, (int)R, median ? 1 : 0)
+                    <= (ll)INT_MAX,
+                "too many (voxel tile, draw tile) blocks for one launch");
+    launch_isc_phase_stat(table.data_ptr<double>(), coef.data_ptr<double>(),
+                          out.data_ptr<double>(), I, V, (int)R, (int)K,
+                          median ? 1 : 0, cur_stream());
+    return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("isc_phase_stat", &isc_phase_stat,
+          "coef [I,R,K] x table [R,K,V] + nanmedian / Fisher mean over R "
+          "-> out [I,V] fp64",
+          pybind11::arg("table"), pybind11::arg("coef"),
+          pybind11::arg("stat"));
+    m.def("isc_phase_max_rows", []() { return isc_phase_max_rows(); },
+          "row cap of the median path of k_isc_phase_stat");
     m.def("isc_resample_stat", &isc_resample_stat,
           "per-draw gather + nanmedian / Fisher mean -> out [I,V] fp64",
           pybind11::arg("table"), pybind11::arg("rows"),
