@@ -333,6 +333,86 @@ class CorrelationPipeline:
             _shrink_(gram)
         return gram
 
+    def _use_fused(self, chunks) -> bool:
+        """Dispatch rule of the single-kernel corr+normalize+Gram path:
+        supported shape, the raw-r/bf16 numerics of ``_raw_split``, and
+        enough selected voxels for one workgroup per CU (below that the
+        duo path's V-split fills the chip better).
+        BRAINIAK_FCMA_FUSED=0 forces the duo path, =1 the fused path at
+        any size."""
+        knob = os.environ.get("BRAINIAK_FCMA_FUSED", "")
+        if not self._raw_split or knob == "0":
+            return False
+        ext = ops.load_extension()
+        if not ext.fcma_corr_gram_fused_supported(
+                self.num_epochs, self.epochs_per_subj,
+                self.data.shape[1]):
+            return False
+        if knob == "1":
+            return True
+        return sum(c for _, c in chunks) >= self._fused_wave()
+
+    def _fused_wave(self) -> int:
+        """Selected voxels that give every CU one fused workgroup."""
+        ext = ops.load_extension()
+        cus = torch.cuda.get_device_properties(
+            self.device).multi_processor_count
+        return ext.fcma_corr_gram_fused_cb() * cus
+
+    def _fused_operands(self):
+        """Time-contiguous copies of the stacked epochs for the fused
+        kernel's MFMA operands, built on first use and kept: the
+        stacked data never changes during the pipeline's life."""
+        if getattr(self, "_fused_ops", None) is None:
+            a = ops.fcma_fused_operand(self.data)
+            b = a if self.data2 is self.data \
+                else ops.fcma_fused_operand(self.data2)
+            self._fused_ops = (a, b)
+        return self._fused_ops
+
+    def _fused_pipeline(self, chunks, shrink=True, consumer=None):
+        """``_duo_pipeline``'s contract on the single-kernel path:
+        consecutive chunks merge into super-chunks of at least one
+        workgroup per CU, one ``fcma_corr_gram_fused`` launch each, and
+        the per-chunk views of its result go to the consumer in chunk
+        order on the current stream."""
+        a_t, b_t = self._fused_operands()
+        E = self.num_epochs
+        P = self.epochs_per_subj
+        ext = ops.load_extension()
+        cb = ext.fcma_corr_gram_fused_cb()
+        wave = self._fused_wave()
+        windows = (b_t.shape[1] + 31) // 32
+        grams = []
+        i = 0
+        while i < len(chunks):
+            j = i + 1
+            start, total = chunks[i]
+            while j < len(chunks) and total < wave \
+                    and chunks[j][0] == start + total:
+                total += chunks[j][1]
+                j += 1
+            # a super-chunk short of one workgroup per CU splits its
+            # column sweep instead (fixed-order partial sums)
+            blocks = (total + cb - 1) // cb
+            nsplit = max(1, min((wave // cb) // blocks, windows))
+            g = ops.fcma_corr_gram_fused(a_t, b_t, start, total, P,
+                                         nsplit=nsplit, shrink=shrink)
+            k0 = 0
+            for s_k, c_k in chunks[i:j]:
+                gk = g[k0:k0 + c_k]
+                if E != g.shape[1]:
+                    gk = gk[:, :E, :E].contiguous()
+                if consumer is not None:
+                    consumer(gk, s_k, c_k)
+                else:
+                    grams.append(gk)
+                k0 += c_k
+            i = j
+        if consumer is not None:
+            return None
+        return torch.cat(grams, dim=0)
+
     def _duo_pipeline(self, chunks, shrink=True, consumer=None):
         """Single-stream duo launches: each kernel carries the raw-corr
         blocks of chunk i AND the Gram(+normalize) blocks of chunk i-1
@@ -347,7 +427,14 @@ class CorrelationPipeline:
         is how the voxel selector overlaps the per-chunk SVM CV with
         the remaining duo sweep.  Grams arrive already shrunk when
         shrink=True (the partial-sum + shrink of chunk i-2 rides the
-        duo grid of launch i as a third block population)."""
+        duo grid of launch i as a third block population).
+
+        When the single-kernel path applies (``_use_fused``) the same
+        contract is served by ``_fused_pipeline`` and the Z workspace
+        is never allocated."""
+        chunks = list(chunks)
+        if self._use_fused(chunks):
+            return self._fused_pipeline(chunks, shrink, consumer)
         ext = ops.load_extension()
         E = self.num_epochs
         Epad = ((E + 63) // 64) * 64

@@ -172,6 +172,39 @@ def fcma_fused_gram(data: torch.Tensor, data2: torch.Tensor, start: int,
                                   int(epochs_per_subj))
 
 
+def fcma_corr_gram_fused_supported(E: int, P: int, L: int) -> bool:
+    """True when ``fcma_corr_gram_fused`` covers E epochs, P epochs per
+    subject and epoch length L (E <= 64, P in {2, 4})."""
+    return bool(_ext().fcma_corr_gram_fused_supported(int(E), int(P),
+                                                      int(L)))
+
+
+def fcma_fused_operand(data: torch.Tensor) -> torch.Tensor:
+    """Time-contiguous operand [64, V, LP] bf16 of stacked epochs
+    data [E, L, V]: epoch rows past E and time steps past L are zero.
+    The single-kernel ``fcma_corr_gram_fused`` reads both of its inputs
+    in this layout; build it once per data set."""
+    E, L, V = data.shape
+    LP = int(_ext().fcma_corr_gram_fused_lp(int(L)))
+    out = torch.zeros((64, V, LP), dtype=torch.bfloat16,
+                      device=data.device)
+    out[:E, :, :L] = data.permute(0, 2, 1)
+    return out
+
+
+def fcma_corr_gram_fused(At_all: torch.Tensor, B_t: torch.Tensor,
+                         start: int, count: int, epochs_per_subj: int,
+                         nsplit: int = 1, shrink: bool = True
+                         ) -> torch.Tensor:
+    """Correlation + normalize + Gram in one kernel over the operands of
+    ``fcma_fused_operand``: [count, 64, 64] fp32 Grams of selected voxels
+    [start, start+count) of At_all against every column of B_t, with the
+    [count, E, V] intermediate kept on chip."""
+    return _ext().fcma_corr_gram_fused(At_all, B_t, int(start), int(count),
+                                       int(epochs_per_subj), int(nsplit),
+                                       bool(shrink))
+
+
 # ---------------------------------------------------------------------------
 # SRM Procrustes
 # ---------------------------------------------------------------------------

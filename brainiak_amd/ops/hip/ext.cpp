@@ -54,6 +54,13 @@ void launch_stencil3d(const float*, const float*, float*, ll, int, int,
                       int, int, void*);
 void launch_fcma_fused_corr_gram(const void*, const void*, float*, ll,
                                  ll, ll, ll, ll, int, void*);
+int fcma_corr_gram_fused_supported(ll, int, ll);
+int fcma_corr_gram_fused_lp(ll);
+int fcma_corr_gram_fused_cb(void);
+int fcma_corr_gram_fused_vt(void);
+void launch_fcma_corr_gram_fused(const void*, const void*, float*, int, ll,
+                                 ll, ll, ll, int, int, int, void*);
+void launch_fcma_gsum(const float*, float*, ll, ll, ll, int, void*);
 void launch_hmm_fb(const double*, const double*, const double*,
                    const double*, const double*, const int*, const int*,
                    double*, double*, ll, int, int, void*);
@@ -392,6 +399,52 @@ torch::Tensor fcma_fused_gram(torch::Tensor A, torch::Tensor B,
     auto G = fcma_gram_bf16(Z, /*norm_P=*/0);
     if (Epad != E)
         return G.narrow(1, 0, E).narrow(2, 0, E).contiguous();
+    return G;
+}
+
+// Single-kernel correlation + normalize + Gram over the cached
+// time-contiguous operands (fcma_fused_kernels.hip).  At_all / B_t are
+// [64, V, LP] bf16: epoch rows past E and time steps past L zero-filled.
+// Returns [count, 64, 64] fp32, shrunk when asked; nsplit > 1 cuts the
+// column sweep into ranges whose partials gsum reduces in fixed order.
+torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
+                                   int64_t start, int64_t count, int64_t P,
+                                   int64_t nsplit, bool shrink) {
+    check_3d(At_all, torch::kBFloat16, "At_all");
+    check_3d(B_t, torch::kBFloat16, "B_t");
+    ll VA = At_all.size(1), VB = B_t.size(1), LP = At_all.size(2);
+    TORCH_CHECK(At_all.size(0) == 64 && B_t.size(0) == 64,
+                "fused operands carry 64 (zero-padded) epoch rows");
+    TORCH_CHECK(B_t.size(2) == LP && (LP == 16 || LP == 32 || LP == 64),
+                "fused operand row length must be 16, 32 or 64");
+    TORCH_CHECK(VB >= 16 && VB % 16 == 0,
+                "data2 voxel count must be a multiple of 16 (host pads)");
+    TORCH_CHECK(P == 2 || P == 4, "fused path needs P in {2,4}");
+    // the kernel keeps per-lane row offsets in 32 bits
+    TORCH_CHECK(VA * LP < (1LL << 31) && VB * LP < (1LL << 31),
+                "voxel count too large for the fused kernel");
+    TORCH_CHECK(start >= 0 && count > 0 && start + count <= VA,
+                "voxel range");
+    ll windows = (VB + fcma_corr_gram_fused_vt() - 1)
+        / fcma_corr_gram_fused_vt();
+    TORCH_CHECK(nsplit >= 1 && nsplit <= windows,
+                "nsplit must be in [1, column windows]");
+    auto opts = At_all.options().dtype(torch::kFloat32);
+    auto G = torch::empty({count, 64, 64}, opts);
+    if (nsplit == 1) {
+        launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
+                                    G.data_ptr<float>(), (int)LP, VA, VB,
+                                    start, count, (int)P, 1,
+                                    shrink ? 1 : 0, cur_stream());
+        return G;
+    }
+    auto Gp = torch::empty({nsplit, count, 64, 64}, opts);
+    launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
+                                Gp.data_ptr<float>(), (int)LP, VA, VB,
+                                start, count, (int)P, (int)nsplit, 0,
+                                cur_stream());
+    launch_fcma_gsum(Gp.data_ptr<float>(), G.data_ptr<float>(), count,
+                     64 * 64, nsplit, shrink ? 1 : 0, cur_stream());
     return G;
 }
 
@@ -824,6 +877,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "per-voxel Gram from bf16 Z [C,E,V]; norm_P>0 applies "
           "Fisher-z + z-score to raw correlations in-tile",
           pybind11::arg("Z"), pybind11::arg("norm_P") = 0);
+    m.def("fcma_corr_gram_fused", &fcma_corr_gram_fused,
+          "single-kernel corr + normalize + Gram over the cached "
+          "[64, V, LP] operands -> [count, 64, 64]",
+          py::arg("At_all"), py::arg("B_t"), py::arg("start"),
+          py::arg("count"), py::arg("P"), py::arg("nsplit") = 1,
+          py::arg("shrink") = true);
+    m.def("fcma_corr_gram_fused_supported",
+          [](int64_t E, int64_t P, int64_t L) {
+              return fcma_corr_gram_fused_supported(E, (int)P, L) != 0;
+          }, "shape envelope of fcma_corr_gram_fused");
+    m.def("fcma_corr_gram_fused_lp",
+          [](int64_t L) { return fcma_corr_gram_fused_lp(L); },
+          "row length of the fused operands for epoch length L");
+    m.def("fcma_corr_gram_fused_cb",
+          []() { return fcma_corr_gram_fused_cb(); },
+          "selected voxels per fused workgroup");
     m.def("fcma_fused_gram_native", &fcma_fused_gram_native,
           "true when the single-kernel corr+gram path covers (E, P, L)");
     m.def("fcma_fused_gram", &fcma_fused_gram,

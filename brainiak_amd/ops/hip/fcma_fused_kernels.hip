@@ -1,0 +1,331 @@
+// k_corr_gram_fused: correlation (MFMA) + Fisher-z / within-subject
+// z-score (registers) + per-voxel Gram (MFMA) in ONE kernel for gfx950.
+// The [count, 64, V] intermediate never leaves the CU: each window of
+// normalized z lives in LDS only.
+//
+// Operands are the time-contiguous cached layout T[64][V][LP] bf16
+// (epoch rows >= E and time steps >= L are zero), LP in {16, 32, 64}.
+//
+// Work split: a 512-thread workgroup (FS_NW = 8 waves, one per CU)
+// owns FS_CB = 16 selected voxels and sweeps a contiguous range of
+// FS_VT = 32-column windows of data2.
+//
+//  phase 1  wave w takes subjects s = w, w+8, ... and both 16-column
+//           sub-tiles.  Per epoch one MFMA (two k-steps for LP = 64) with
+//             A (M = column v)  : lane l -> T2[e][v0 + l%16][k-seg(l)]
+//             B (N = voxel  c)  : lane l -> T1[e][c0 + l%16][k-seg(l)]
+//           so the accumulator holds c = lane&15 on the lane and the
+//           four consecutive columns v = 4*(lane>>4) + reg in its regs.
+//           The P accumulators of a subject sit in the same lane.
+//  phase 2  per element: r -> bf16 -> fp32, fisher_z_unscaled_bf16r,
+//           biased mean/var over P, (z - mean) * rsq(var) (var <= 0 ->
+//           0; var is never denormal, so the raw v_rsq_f32 equals
+//           rsqrtf bit for bit), bf16; the 4 columns pack into one
+//           8-byte LDS store into z[c][e][v].
+//  phase 3  wave w owns voxels 2w, 2w+1: four 16-row bands as bf16x8
+//           fragments, the 10 upper-triangle 16x16x32 MFMAs per voxel;
+//           accumulators (40 fp32 / voxel / lane) persist across the
+//           sweep and the lower triangle is mirrored at the store.
+//
+// The z image is double-buffered, so there is ONE barrier per window:
+// a wave that leaves the Gram of window w early starts the correlation
+// and normalize of window w+1 while its neighbours still issue MFMAs.
+// (Four waves x four voxels at two blocks per CU needs 160 accumulator
+// registers per lane and spills; eight waves x two voxels does not.)
+//
+// LDS image: row (c, e) is 64 B = four 16-B chunks, chunk index XORed
+// with (e>>2)&3 so the Gram's ds_read_b128 (16 rows x one chunk per
+// 16-lane group) touches 16 distinct slots; the per-voxel stride is
+// 4096 + 32 B so the 16 voxels of a phase-2 store spread over the banks.
+
+#include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+
+#include "fcma_common.h"
+
+#define FS_CB 16
+#define FS_VT 32
+#define FS_E 64
+#define FS_NW 8                                // waves per workgroup
+#define FS_VPW (FS_CB / FS_NW)                 // Gram voxels per wave
+#define FS_CSTRIDE (FS_E * FS_VT * 2 + 32)     // bytes per voxel image
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 nbf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 nbf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 nbf16x8 __attribute__((ext_vector_type(8)));
+
+// one lane's k-segment of a [.., LP] row: 4 bf16 for the 16x16x16
+// form (LP == 16), 8 bf16 per 16x16x32 k-step otherwise
+template <int LP> struct FragT { bf16x8 v; };
+template <> struct FragT<16> { bf16x4 v; };
+
+template <int LP>
+__device__ __forceinline__ FragT<LP> load_frag(const bf16_t* row, int q,
+                                               int ks) {
+    FragT<LP> f;
+    if constexpr (LP == 16)
+        f.v = *(const bf16x4*)(row + 4 * q);
+    else
+        f.v = *(const bf16x8*)(row + 32 * ks + 8 * q);
+    return f;
+}
+
+template <int LP>
+__device__ __forceinline__ f32x4 corr_mfma(const FragT<LP>& a,
+                                           const FragT<LP>& b, f32x4 acc) {
+    if constexpr (LP == 16) {
+        // v_mfma_f32_16x16x16_bf16: lane l, j in 0..3 ->
+        // A[l%16][4*(l>>4)+j], B[4*(l>>4)+j][l%16]
+        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a.v, b.v, acc,
+                                                         0, 0, 0);
+    } else {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            __builtin_bit_cast(nbf16x8, a.v),
+            __builtin_bit_cast(nbf16x8, b.v), acc, 0, 0, 0);
+    }
+}
+
+template <int TP, int LP>
+__global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
+    const bf16_t* __restrict__ T1, const bf16_t* __restrict__ T2,
+    float* __restrict__ Gout, ll VA, ll VB, ll s0, ll C, int nsplit,
+    int do_shrink) {
+    constexpr int P = TP;
+    constexpr int NSUBJ = FS_E / P;
+    constexpr int SPW = NSUBJ / FS_NW;           // subjects per wave
+    constexpr int KS = (LP + 31) / 32;         // MFMA k-steps
+
+    const ll vs = blockIdx.x % nsplit;
+    const ll ct = blockIdx.x / nsplit;
+    const ll c0 = ct * FS_CB;
+    if (c0 >= C) return;
+    const ll wAll = (VB + FS_VT - 1) / FS_VT;
+    const ll wPer = (wAll + nsplit - 1) / nsplit;
+    const ll w0 = vs * wPer;
+    const ll w1 = min(wAll, w0 + wPer);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    // wave index in an SGPR: everything derived from it (subject, epoch
+    // row bases, LDS rows) then stays on the scalar unit
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l16 = lane & 15;
+    const int q = lane >> 4;
+
+    __shared__ __attribute__((aligned(16)))
+        unsigned char zbuf[2][FS_CB * FS_CSTRIDE];
+
+    // selected voxel of this lane (clamped: tail lanes recompute the
+    // last voxel and are never stored)
+    const ll csel = s0 + min(c0 + (ll)l16, C - 1);
+
+    // wave-uniform row base + per-lane 32-bit element offset
+    const unsigned sel_off = (unsigned)(csel * LP);
+    const unsigned col_off = (unsigned)(l16 * LP);
+    auto sel_row = [&](int e) {
+        return T1 + (ll)e * VA * LP + sel_off;
+    };
+    auto col_row = [&](int e, ll v) {
+        return T2 + ((ll)e * VB + v) * LP + col_off;
+    };
+
+    f32x4 G[FS_VPW][10];
+    #pragma unroll
+    for (int i = 0; i < FS_VPW; ++i)
+        #pragma unroll
+        for (int t = 0; t < 10; ++t) G[i][t] = (f32x4)0.f;
+
+    // task (si, st): subject wv + FS_NW*si, 16-column sub-tile st
+    auto load_cols = [&](ll v0, int si, int st, int ks, FragT<LP> dst[P]) {
+        const int s = wv + FS_NW * si;
+        // columns past VB (VB % 16 == 0, so whole sub-tiles) read the
+        // last valid rows; their z is forced to 0 below
+        ll v = v0 + st * 16;
+        v = (v < VB) ? v : VB - 16;
+        #pragma unroll
+        for (int p = 0; p < P; ++p)
+            dst[p] = load_frag<LP>(col_row(s * P + p, v), q, ks);
+    };
+
+    FragT<LP> cur[P], nxt[P];
+    if (w0 < w1) load_cols(w0 * FS_VT, 0, 0, 0, cur);
+
+    for (ll w = w0; w < w1; ++w) {
+        const ll v0 = w * FS_VT;
+        unsigned char* zimg = zbuf[(w - w0) & 1];
+        #pragma unroll 1
+        for (int si = 0; si < SPW; ++si) {
+            const int s = wv + FS_NW * si;
+            FragT<LP> sel[P];
+            #pragma unroll
+            for (int p = 0; p < P; ++p)
+                sel[p] = load_frag<LP>(sel_row(s * P + p), q, 0);
+            #pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                // issue the next task's column loads before this
+                // task's MFMA + normalize: their latency hides under
+                // the VALU work
+                if (st == 0) load_cols(v0, si, 1, 0, nxt);
+                else if (si + 1 < SPW) load_cols(v0, si + 1, 0, 0, nxt);
+                else if (w + 1 < w1) load_cols(v0 + FS_VT, 0, 0, 0, nxt);
+
+                const bool live = (v0 + st * 16) < VB;   // wave-uniform
+                f32x4 r[P];
+                #pragma unroll
+                for (int p = 0; p < P; ++p)
+                    r[p] = corr_mfma<LP>(cur[p], sel[p], (f32x4)0.f);
+                if constexpr (KS == 2) {
+                    FragT<LP> c2[P];
+                    load_cols(v0, si, st, 1, c2);
+                    #pragma unroll
+                    for (int p = 0; p < P; ++p) {
+                        FragT<LP> b2 =
+                            load_frag<LP>(sel_row(s * P + p), q, 1);
+                        r[p] = corr_mfma<LP>(c2[p], b2, r[p]);
+                    }
+                }
+                // r goes through bf16: same quantisation points as the
+                // raw-correlation tensor of the streamed path.  Two
+                // per convert, unpacked with a shift and a mask.
+                f32x4 rq[P];
+                #pragma unroll
+                for (int p = 0; p < P; ++p)
+                    #pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        f32x2 pr = {r[p][2 * h], r[p][2 * h + 1]};
+                        unsigned u = __builtin_bit_cast(
+                            unsigned, __builtin_convertvector(pr, nbf16x2));
+                        rq[p][2 * h] = __builtin_bit_cast(float, u << 16);
+                        rq[p][2 * h + 1] =
+                            __builtin_bit_cast(float, u & 0xffff0000u);
+                    }
+                nbf16x4 zo[P];
+                #pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float z[P];
+                    float mean = 0.f, sq = 0.f;
+                    #pragma unroll
+                    for (int p = 0; p < P; ++p) {
+                        z[p] = fisher_z_unscaled_bf16r(rq[p][i]);
+                        mean += z[p]; sq += z[p] * z[p];
+                    }
+                    mean /= (float)P;
+                    float var = sq / (float)P - mean * mean;
+                    float inv = (var <= 0.f) ? 0.f : __builtin_amdgcn_rsqf(var);
+                    if (!live) inv = 0.f;
+                    #pragma unroll
+                    for (int p = 0; p < P; ++p)
+                        zo[p][i] = (__bf16)((z[p] - mean) * inv);
+                }
+                // 8-byte store: columns st*16 + 4q .. +3 of row (c, e)
+                const int chunk = st * 2 + (q >> 1);
+                #pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const int e = s * P + p;
+                    unsigned char* dst = zimg + l16 * FS_CSTRIDE + e * 64
+                        + ((chunk ^ ((e >> 2) & 3)) << 4) + (q & 1) * 8;
+                    *(nbf16x4*)dst = zo[p];
+                }
+                #pragma unroll
+                for (int p = 0; p < P; ++p) cur[p] = nxt[p];
+            }
+        }
+        // window image complete.  The other buffer is free: every wave
+        // passed this barrier after its Gram reads of the window before
+        __syncthreads();
+
+        #pragma unroll
+        for (int i = 0; i < FS_VPW; ++i) {
+            const unsigned char* zc =
+                zimg + (wv * FS_VPW + i) * FS_CSTRIDE;
+            nbf16x8 f[4];
+            #pragma unroll
+            for (int bnd = 0; bnd < 4; ++bnd) {
+                const int e = bnd * 16 + l16;
+                f[bnd] = *(const nbf16x8*)(
+                    zc + e * 64 + ((q ^ ((e >> 2) & 3)) << 4));
+            }
+            int t = 0;
+            #pragma unroll
+            for (int bi = 0; bi < 4; ++bi)
+                #pragma unroll
+                for (int bj = bi; bj < 4; ++bj, ++t)
+                    G[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        f[bi], f[bj], G[i][t], 0, 0, 0);
+        }
+    }
+
+    // epilogue: this block owns G (nsplit == 1, optionally shrunk the
+    // way gsum_body does it) or one [count, 64, 64] partial slab
+    #pragma unroll
+    for (int i = 0; i < FS_VPW; ++i) {
+        const ll c = c0 + wv * FS_VPW + i;
+        if (c >= C) continue;                  // wave-uniform
+        float scale = 1.0f;
+        if (do_shrink) {
+            float lead = __shfl(G[i][0][0], 0);
+            lead = fmaxf(fabsf(lead), 1.0f);
+            float digits = floorf(log10f(lead)) + 1.0f;
+            if (digits > 2.0f)
+                scale = powf(10.0f, 2.0f - digits);
+        }
+        float* Gc = Gout + (vs * C + c) * (ll)(FS_E * FS_E);
+        const int drow = q * 4;
+        int t = 0;
+        #pragma unroll
+        for (int bi = 0; bi < 4; ++bi)
+            #pragma unroll
+            for (int bj = bi; bj < 4; ++bj, ++t) {
+                f32x4 val = G[i][t] * scale;
+                #pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    Gc[(bi * 16 + drow + r) * FS_E + bj * 16 + l16] =
+                        val[r];
+                if (bi != bj)
+                    *(f32x4*)&Gc[(bj * 16 + l16) * FS_E + bi * 16 + drow]
+                        = val;
+            }
+    }
+}
+
+static int fused_lp(ll L) {
+    return L <= 16 ? 16 : (L <= 32 ? 32 : 64);
+}
+
+extern "C" int fcma_corr_gram_fused_supported(ll E, int P, ll L) {
+    return E > 0 && E <= FS_E && (P == 2 || P == 4) && E % P == 0
+        && L > 0 && L <= 64;
+}
+
+// row length of the cached time-contiguous layout for epoch length L
+extern "C" int fcma_corr_gram_fused_lp(ll L) { return fused_lp(L); }
+
+extern "C" int fcma_corr_gram_fused_cb(void) { return FS_CB; }
+extern "C" int fcma_corr_gram_fused_vt(void) { return FS_VT; }
+
+extern "C" void launch_fcma_corr_gram_fused(
+    const void* T1, const void* T2, float* Gout, int LP, ll VA, ll VB,
+    ll s0, ll C, int P, int nsplit, int do_shrink, hipStream_t stream) {
+    ll grid = ((C + FS_CB - 1) / FS_CB) * nsplit;
+    #define FS_ONE(TP, TLP)                                              \
+        hipLaunchKernelGGL((k_corr_gram_fused<TP, TLP>), dim3(grid),     \
+                           dim3(64 * FS_NW), 0, stream,                  \
+                           (const bf16_t*)T1,                            \
+                           (const bf16_t*)T2, Gout, VA, VB, s0, C,       \
+                           nsplit, do_shrink)
+    if (P == 4) {
+        switch (LP) {
+            case 16: FS_ONE(4, 16); return;
+            case 32: FS_ONE(4, 32); return;
+            case 64: FS_ONE(4, 64); return;
+        }
+    } else if (P == 2) {
+        switch (LP) {
+            case 16: FS_ONE(2, 16); return;
+            case 32: FS_ONE(2, 32); return;
+            case 64: FS_ONE(2, 64); return;
+        }
+    }
+    #undef FS_ONE
+}

@@ -27,14 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define WAVE 64
-typedef __hip_bfloat16 bf16_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-// 4-byte-aligned variant for global loads: gfx950 dwordx4 loads need
-// only dword alignment, and bf16 rows are 4B- but not 16B-aligned
-typedef short bf16x8_u __attribute__((ext_vector_type(8), aligned(4)));
-typedef long long ll;
+#include "fcma_common.h"
 
 // --- fp8 (OCP e4m3fn) Z-tile path -----------------------------------------
 // The normalized Z values are within-subject z-scores, bounded by
@@ -60,30 +53,6 @@ __device__ __forceinline__ bf16_t z_cast<bf16_t>(float v) {
 template <>
 __device__ __forceinline__ fp8_t z_cast<fp8_t>(float v) {
     return to_fp8(v);
-}
-
-// ---------------------------------------------------------------------------
-// MFMA fragment maps, v_mfma_f32_16x16x32_bf16 (gfx950):
-//   A (16x32): lane l, j in 0..7 -> A[l%16][frag_k(l,j)]
-//   B (32x16): lane l, j in 0..7 -> B[frag_k(l,j)][l%16]
-//   C/D (16x16, f32x4): col = lane&15, row = (lane>>4)*4 + reg
-// frag_k isolated so a layout flip is one line, guarded by GPU numerics
-// tests (tests/ops/test_hip_ops.py::test_gram_identity_asymmetric).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int frag_k(int lane, int j) {
-    return 8 * (lane >> 4) + j;
-}
-
-// scale-free Fisher z: log2(num) - log2(den).  The downstream
-// within-subject z-score (z - mean) * rsqrt(var) is invariant to the
-// 0.5*ln2 factor, so the kernels that always z-score skip the multiply
-// (one VALU op per element on an issue-bound kernel).
-__device__ __forceinline__ float fisher_z_unscaled(float r) {
-    float num = 1.0f + r;
-    float den = 1.0f - r;
-    num = (num <= 0.0f) ? 1e-4f : num;
-    den = (den <= 0.0f) ? 1e-4f : den;
-    return __builtin_amdgcn_logf(num) - __builtin_amdgcn_logf(den);
 }
 
 __device__ __forceinline__ float fisher_z(float r) {
@@ -2344,4 +2313,19 @@ extern "C" void launch_fcma_gram_f32(const float* Z, float* G, ll C, ll E,
     ll grid = C * eb * eb;
     hipLaunchKernelGGL(k_gram_f32, dim3(grid), dim3(256), 0, stream,
                        Z, G, C, E, V);
+}
+
+// stand-alone gsum: fixed-order reduction (+ shrink) of [nsplit, C, E, E]
+// partials for callers that have no duo grid to ride
+__global__ __launch_bounds__(256) void k_gsum(
+    const float* __restrict__ Gp, float* __restrict__ Gout, ll Cs, ll EE,
+    ll nsplit, int do_shrink) {
+    gsum_body(blockIdx.x, Gp, Gout, Cs, EE, nsplit, do_shrink);
+}
+
+extern "C" void launch_fcma_gsum(const float* Gp, float* Gout, ll Cs,
+                                 ll EE, ll nsplit, int do_shrink,
+                                 hipStream_t stream) {
+    hipLaunchKernelGGL(k_gsum, dim3(Cs), dim3(256), 0, stream, Gp, Gout,
+                       Cs, EE, nsplit, do_shrink);
 }

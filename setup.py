@@ -21,6 +21,7 @@ ext = CUDAExtension(
     sources=[
         os.path.join(HIP_DIR, "ext.cpp"),
         os.path.join(HIP_DIR, "fcma_kernels.hip"),
+        os.path.join(HIP_DIR, "fcma_fused_kernels.hip"),
         os.path.join(HIP_DIR, "svm_kernels.hip"),
         os.path.join(HIP_DIR, "isfc_kernels.hip"),
         os.path.join(HIP_DIR, "stencil_kernels.hip"),
