@@ -203,10 +203,10 @@ def _accuracy_gpu(kernels: torch.Tensor, labels: np.ndarray, num_folds: int,
 
 
 def _accuracy_one_voxel_sklearn(args):
-    kernel, labels, num_folds, C, class_weight = args
+    kernel, labels, num_folds, C, class_weight, tol = args
     from sklearn import model_selection, svm
     clf = svm.SVC(kernel='precomputed', shrinking=False, C=C,
-                  class_weight=class_weight)
+                  class_weight=class_weight, tol=tol)
     skf = model_selection.StratifiedKFold(n_splits=num_folds, shuffle=False)
     scores = model_selection.cross_val_score(clf, kernel, y=labels, cv=skf,
                                              n_jobs=1)
@@ -226,7 +226,7 @@ def cross_validate_voxels(kernels: torch.Tensor, labels: np.ndarray,
     if kernels.is_cuda:
         return _accuracy_gpu(kernels, labels, num_folds, C, tol)
     k_np = kernels.cpu().numpy().astype(np.float64)
-    jobs = [(k_np[i], labels, num_folds, C, None)
+    jobs = [(k_np[i], labels, num_folds, C, None, tol)
             for i in range(k_np.shape[0])]
     if process_num and len(jobs) > 8:
         with multiprocessing.Pool(process_num) as pool:

@@ -25,6 +25,10 @@ factoranalysis/tfa_extension.cpp, eventseg/_utils.pyx):
                           block with a fixed spectral table + the same
                           median / Fisher mean: the null distribution of
                           the ISC phase-randomisation test
+ - ``searchlight_gram`` — per-centre [E,E] Gram of a searchlight's
+                          activity vectors (gather + exact-fp32 MFMA
+                          syrk), the front end of the activity-based
+                          voxel selector
 
 Build: ``python setup.py build_ext --inplace`` (hipcc, gfx950) or
 ``__graft_entry__.build()``.  The extension is REQUIRED whenever CUDA
@@ -57,6 +61,10 @@ __all__ = [
     "isc_resample_max_rows",
     "isc_resample_stat",
     "isfc_accum_",
+    "searchlight_gram",
+    "searchlight_gram_kernel",
+    "searchlight_gram_max_e",
+    "searchlight_gram_torch",
     "stencil3d",
     "load_extension",
     "masked_log",
@@ -395,6 +403,114 @@ def stencil3d(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Valid [K,K,K] stencil over [B,X,Y,Z] fp32 (K odd, <= 9) — the
     searchlight ball aggregation without MIOpen's im2col detour."""
     return _ext().stencil3d(x, w)
+
+
+# ---------------------------------------------------------------------------
+# activity-based searchlight Gram
+# ---------------------------------------------------------------------------
+
+# bytes of gathered rows the torch twin holds per chunk of centres
+_SL_GRAM_TWIN_BYTES = 1 << 28
+
+
+def searchlight_gram_max_e() -> int:
+    """Largest epoch count E that ``searchlight_gram_kernel`` takes (its
+    upper-triangular tile accumulators live in registers)."""
+    return int(_ext().searchlight_gram_max_e())
+
+
+def searchlight_gram_kernel(x: torch.Tensor, mask: torch.Tensor,
+                            shape: torch.Tensor,
+                            centres: torch.Tensor) -> torch.Tensor:
+    """The HIP kernel behind ``searchlight_gram`` (one workgroup per
+    centre, exact-fp32 MFMA).  x fp32 [B, X, Y, Z, E], mask uint8
+    [B, X, Y, Z], shape uint8 [K, K, K], centres int64 [N]; all
+    contiguous on one GPU, E <= ``searchlight_gram_max_e()``.  Centre
+    positions are NOT checked here."""
+    return _ext().searchlight_gram(x, mask, shape, centres)
+
+
+def searchlight_gram_torch(x: torch.Tensor, mask: torch.Tensor,
+                           shape: torch.Tensor,
+                           centres: torch.Tensor) -> torch.Tensor:
+    """Torch twin of ``searchlight_gram_kernel``: gathers each centre's
+    K^3 neighbourhood (the offsets the shape keeps), zeroes the rows the
+    mask drops and runs one ``bmm`` per chunk of centres.  Works in fp64
+    on CPU tensors and in fp32 on the GPU; returns fp32 [N, E, E] with
+    the lower triangle mirrored from the upper."""
+    B, X, Y, Z, E = x.shape
+    K = shape.shape[0]
+    rad = K // 2
+    dev = x.device
+    work = torch.float32 if x.is_cuda else torch.float64
+    ar = torch.arange(K, device=dev) - rad
+    rel = ((ar[:, None, None] * Y + ar[None, :, None]) * Z
+           + ar[None, None, :]).reshape(-1)
+    rel = rel[shape.reshape(-1).to(torch.bool)]
+    rows = x.reshape(-1, E)
+    live = mask.reshape(-1).to(torch.bool)
+    N = centres.shape[0]
+    out = torch.empty((N, E, E), dtype=torch.float32, device=dev)
+    per_centre = max(1, rel.numel()) * E * (4 if x.is_cuda else 8)
+    step = max(1, _SL_GRAM_TWIN_BYTES // per_centre)
+    for lo in range(0, N, step):
+        idx = centres[lo:lo + step, None] + rel[None, :]
+        a = rows[idx].to(work)
+        a = torch.where(live[idx][:, :, None], a, torch.zeros_like(a))
+        g = torch.bmm(a.transpose(1, 2), a)
+        g = torch.triu(g) + torch.triu(g, 1).transpose(1, 2)
+        out[lo:lo + step] = g.to(torch.float32)
+    return out
+
+
+def searchlight_gram(x: torch.Tensor, mask: torch.Tensor,
+                     shape: torch.Tensor,
+                     centres: torch.Tensor) -> torch.Tensor:
+    """Gram matrices of the activity vectors of a list of searchlights:
+
+        G[n, e, f] = sum over v in shape(c_n) & mask of x[v, e] * x[v, f]
+
+    x [B, X, Y, Z, E] fp32 halo-padded block stack (epoch innermost);
+    mask [B, X, Y, Z] bool or uint8; shape [K, K, K] bool or uint8 with
+    K = 2 rad + 1 odd and at most 9; centres [N] int64 linear indices of
+    the centre voxels in [B, X, Y, Z].  Returns G [N, E, E] fp32 with
+    G == G^T bit for bit.
+
+    Raises ValueError for a shape that is not such a cube and for a
+    centre that is out of range or within rad of a block face.  GPU
+    tensors with E <= ``searchlight_gram_max_e()`` run the HIP kernel;
+    everything else, and everything under ``BRAINIAK_SL_GRAM=torch``,
+    runs ``searchlight_gram_torch``.
+    """
+    if x.dim() != 5 or mask.shape != x.shape[:4]:
+        raise ValueError("x must be [B, X, Y, Z, E] and mask [B, X, Y, Z]")
+    K = shape.shape[0] if shape.dim() == 3 else 0
+    if K == 0 or tuple(shape.shape) != (K, K, K) or K % 2 == 0 or K > 9:
+        raise ValueError("shape must be a [K, K, K] cube with odd K <= 9")
+    B, X, Y, Z, E = x.shape
+    rad = K // 2
+    if centres.dim() != 1:
+        raise ValueError("centres must be a 1-D index list")
+    centres = centres.to(device=x.device, dtype=torch.int64).contiguous()
+    if centres.numel():
+        k = centres % Z
+        j = (centres // Z) % Y
+        i = (centres // (Y * Z)) % X
+        bad = (centres < 0) | (centres >= B * X * Y * Z)
+        for pos, edge in ((i, X), (j, Y), (k, Z)):
+            bad |= (pos < rad) | (pos >= edge - rad)
+        if bool(bad.any()):
+            raise ValueError(
+                "searchlight centre out of range or within the radius "
+                "of a block face")
+    mask = mask.to(torch.uint8)
+    shape = shape.to(device=x.device, dtype=torch.uint8)
+    if (x.is_cuda and os.environ.get("BRAINIAK_SL_GRAM") != "torch"
+            and require_hip() and E <= searchlight_gram_max_e()):
+        return searchlight_gram_kernel(
+            x.to(torch.float32).contiguous(), mask.contiguous(),
+            shape.contiguous(), centres)
+    return searchlight_gram_torch(x, mask, shape, centres)
 
 
 def isfc_accum_(acc: torch.Tensor, M: torch.Tensor) -> torch.Tensor:

@@ -77,6 +77,10 @@ void launch_isc_phase_stat(const double*, const double*, double*, ll, ll,
                            int, int, int, void*);
 int isc_phase_max_rows(void);
 ll isc_phase_blocks(ll, ll, int, int);
+void launch_sl_gram(const float*, const unsigned char*,
+                    const unsigned char*, const ll*, float*, ll, int, int,
+                    int, int, void*);
+int sl_gram_max_e(void);
 }
 
 static void* cur_stream() {
@@ -812,7 +816,59 @@ torch::Tensor isc_phase_stat(torch::Tensor table, torch::Tensor coef,
     return out;
 }
 
+torch::Tensor searchlight_gram(torch::Tensor x, torch::Tensor mask,
+                               torch::Tensor shape, torch::Tensor centres) {
+    // per-centre Gram of the searchlight's activity vectors
+    // (searchlight_gram.hip::k_sl_gram).  Centre positions are NOT
+    // checked here (ops.searchlight_gram checks them on the host).
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 5
+                && x.scalar_type() == torch::kFloat32,
+                "x must be contiguous fp32 [B,X,Y,Z,E] on the GPU");
+    TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() && mask.dim() == 4
+                && mask.scalar_type() == torch::kUInt8
+                && mask.device() == x.device()
+                && mask.sizes() == x.sizes().slice(0, 4),
+                "mask must be contiguous uint8 [B,X,Y,Z] on x's GPU");
+    TORCH_CHECK(shape.is_cuda() && shape.is_contiguous() && shape.dim() == 3
+                && shape.scalar_type() == torch::kUInt8
+                && shape.device() == x.device(),
+                "shape must be contiguous uint8 [K,K,K] on x's GPU");
+    TORCH_CHECK(centres.is_cuda() && centres.is_contiguous()
+                && centres.dim() == 1
+                && centres.scalar_type() == torch::kInt64
+                && centres.device() == x.device(),
+                "centres must be contiguous int64 [N] on x's GPU");
+    ll K = shape.size(0);
+    TORCH_CHECK(shape.size(1) == K && shape.size(2) == K && K % 2 == 1
+                && K <= 9, "shape must be cubic with odd K <= 9");
+    ll X = x.size(1), Y = x.size(2), Z = x.size(3), E = x.size(4);
+    ll N = centres.size(0);
+    TORCH_CHECK(E >= 1 && E <= sl_gram_max_e(),
+                "searchlight_gram takes 1 <= E <= ", sl_gram_max_e(),
+                " (got ", E, ")");
+    TORCH_CHECK(X >= K && Y >= K && Z >= K,
+                "block smaller than the searchlight shape");
+    // offsets inside one block are 32-bit; the block base is 64-bit
+    TORCH_CHECK(X * Y * Z <= (ll)INT_MAX, "block too large");
+    TORCH_CHECK(N <= (ll)INT_MAX, "too many centres for one launch");
+    auto G = torch::empty({N, E, E}, x.options());
+    if (N == 0) return G;
+    launch_sl_gram(x.data_ptr<float>(), mask.data_ptr<uint8_t>(),
+                   shape.data_ptr<uint8_t>(),
+                   (const ll*)centres.data_ptr<int64_t>(),
+                   G.data_ptr<float>(), N, (int)Y, (int)Z, (int)E, (int)K,
+                   cur_stream());
+    return G;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("searchlight_gram", &searchlight_gram,
+          "per-centre Gram of the searchlight's activity vectors "
+          "-> G [N,E,E] fp32",
+          pybind11::arg("x"), pybind11::arg("mask"), pybind11::arg("shape"),
+          pybind11::arg("centres"));
+    m.def("searchlight_gram_max_e", []() { return sl_gram_max_e(); },
+          "epoch cap of k_sl_gram");
     m.def("isc_phase_stat", &isc_phase_stat,
           "coef [I,R,K] x table [R,K,V] + nanmedian / Fisher mean over R "
           "-> out [I,V] fp64",
