@@ -202,15 +202,20 @@ def fcma_fused_operand(data: torch.Tensor) -> torch.Tensor:
 
 def fcma_corr_gram_fused(At_all: torch.Tensor, B_t: torch.Tensor,
                          start: int, count: int, epochs_per_subj: int,
-                         nsplit: int = 1, shrink: bool = True
-                         ) -> torch.Tensor:
+                         nsplit: int = 1, shrink: bool = True,
+                         clamp: str = "auto") -> torch.Tensor:
     """Correlation + normalize + Gram in one kernel over the operands of
     ``fcma_fused_operand``: [count, 64, 64] fp32 Grams of selected voxels
     [start, start+count) of At_all against every column of B_t, with the
-    [count, E, V] intermediate kept on chip."""
+    [count, E, V] intermediate kept on chip.
+
+    The operands must be finite (``stack_epochs`` zero-pads, callers
+    z-score with a clamped std).  ``clamp="auto"`` applies the Fisher-z
+    clamp only where a correlation reaches |r| >= 1; ``clamp="always"``
+    applies it to every element.  Both give the same bits."""
     return _ext().fcma_corr_gram_fused(At_all, B_t, int(start), int(count),
                                        int(epochs_per_subj), int(nsplit),
-                                       bool(shrink))
+                                       bool(shrink), str(clamp))
 
 
 # ---------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <climits>
+#include <string>
 
 typedef long long ll;
 
@@ -59,7 +60,7 @@ int fcma_corr_gram_fused_lp(ll);
 int fcma_corr_gram_fused_cb(void);
 int fcma_corr_gram_fused_vt(void);
 void launch_fcma_corr_gram_fused(const void*, const void*, float*, int, ll,
-                                 ll, ll, ll, int, int, int, void*);
+                                 ll, ll, ll, int, int, int, int, void*);
 void launch_fcma_gsum(const float*, float*, ll, ll, ll, int, void*);
 void launch_hmm_fb(const double*, const double*, const double*,
                    const double*, const double*, const int*, const int*,
@@ -411,9 +412,12 @@ torch::Tensor fcma_fused_gram(torch::Tensor A, torch::Tensor B,
 // [64, V, LP] bf16: epoch rows past E and time steps past L zero-filled.
 // Returns [count, 64, 64] fp32, shrunk when asked; nsplit > 1 cuts the
 // column sweep into ranges whose partials gsum reduces in fixed order.
+// clamp = "auto" clamps the Fisher z only in tasks that hold an |r| >= 1;
+// "always" clamps every element (same bits for finite operands).
 torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
                                    int64_t start, int64_t count, int64_t P,
-                                   int64_t nsplit, bool shrink) {
+                                   int64_t nsplit, bool shrink,
+                                   const std::string& clamp) {
     check_3d(At_all, torch::kBFloat16, "At_all");
     check_3d(B_t, torch::kBFloat16, "B_t");
     ll VA = At_all.size(1), VB = B_t.size(1), LP = At_all.size(2);
@@ -433,20 +437,24 @@ torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
         / fcma_corr_gram_fused_vt();
     TORCH_CHECK(nsplit >= 1 && nsplit <= windows,
                 "nsplit must be in [1, column windows]");
+    TORCH_CHECK(clamp == "auto" || clamp == "always",
+                "clamp must be \"auto\" or \"always\"");
+    const int force_clamp = clamp == "always" ? 1 : 0;
     auto opts = At_all.options().dtype(torch::kFloat32);
     auto G = torch::empty({count, 64, 64}, opts);
     if (nsplit == 1) {
         launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
                                     G.data_ptr<float>(), (int)LP, VA, VB,
                                     start, count, (int)P, 1,
-                                    shrink ? 1 : 0, cur_stream());
+                                    shrink ? 1 : 0, force_clamp,
+                                    cur_stream());
         return G;
     }
     auto Gp = torch::empty({nsplit, count, 64, 64}, opts);
     launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
                                 Gp.data_ptr<float>(), (int)LP, VA, VB,
                                 start, count, (int)P, (int)nsplit, 0,
-                                cur_stream());
+                                force_clamp, cur_stream());
     launch_fcma_gsum(Gp.data_ptr<float>(), G.data_ptr<float>(), count,
                      64 * 64, nsplit, shrink ? 1 : 0, cur_stream());
     return G;
@@ -938,7 +946,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "[64, V, LP] operands -> [count, 64, 64]",
           py::arg("At_all"), py::arg("B_t"), py::arg("start"),
           py::arg("count"), py::arg("P"), py::arg("nsplit") = 1,
-          py::arg("shrink") = true);
+          py::arg("shrink") = true, py::arg("clamp") = "auto");
     m.def("fcma_corr_gram_fused_supported",
           [](int64_t E, int64_t P, int64_t L) {
               return fcma_corr_gram_fused_supported(E, (int)P, L) != 0;

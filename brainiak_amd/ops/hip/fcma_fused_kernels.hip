@@ -5,6 +5,9 @@
 //
 // Operands are the time-contiguous cached layout T[64][V][LP] bf16
 // (epoch rows >= E and time steps >= L are zero), LP in {16, 32, 64}.
+// They must be finite: stack_epochs zero-pads and callers z-score with
+// a clamped std.  The clamp test below looks for |r| >= 1 and does not
+// see a NaN.
 //
 // Work split: a 512-thread workgroup (FS_NW = 8 waves, one per CU)
 // owns FS_CB = 16 selected voxels and sweeps a contiguous range of
@@ -17,11 +20,18 @@
 //           so the accumulator holds c = lane&15 on the lane and the
 //           four consecutive columns v = 4*(lane>>4) + reg in its regs.
 //           The P accumulators of a subject sit in the same lane.
-//  phase 2  per element: r -> bf16 -> fp32, fisher_z_unscaled_bf16r,
-//           biased mean/var over P, (z - mean) * rsq(var) (var <= 0 ->
-//           0; var is never denormal, so the raw v_rsq_f32 equals
-//           rsqrtf bit for bit), bf16; the 4 columns pack into one
-//           8-byte LDS store into z[c][e][v].
+//           The wave's B fragments (its subjects' selected-voxel rows)
+//           are the same for every window: they are loaded once and
+//           stay in registers for the sweep.
+//  phase 2  per element: r -> bf16 -> fp32, Fisher z, biased mean/var
+//           over P, (z - mean) * rsq(var) (var <= 0 -> 0; var is never
+//           denormal, so the raw v_rsq_f32 equals rsqrtf bit for bit),
+//           bf16; the 4 columns pack into one 8-byte LDS store into
+//           z[c][e][v].  The clamp of the Fisher z (max(1 +- r, 1e-4))
+//           only matters where the bf16 r reaches |r| >= 1, so a task
+//           takes the clamped normalize only when a ballot finds such
+//           an r in the wave; force_clamp takes it for every task.
+//           Both give the same bits.
 //  phase 3  wave w owns voxels 2w, 2w+1: four 16-row bands as bf16x8
 //           fragments, the 10 upper-triangle 16x16x32 MFMAs per voxel;
 //           accumulators (40 fp32 / voxel / lane) persist across the
@@ -86,11 +96,78 @@ __device__ __forceinline__ f32x4 corr_mfma(const FragT<LP>& a,
     }
 }
 
+// Fisher z + within-subject z-score of one task: the P x 4 bf16-rounded
+// correlations of one lane (four columns x the P epochs of a subject)
+// -> P packed bf16x4.  CLAMP = true is fisher_z_unscaled_bf16r, CLAMP =
+// false drops its two max(): for |r| < 1 on the bf16 grid 1 +- r is at
+// least 2^-8, so the clamp is the identity and both forms give the
+// same bits.  The columns go as the two pairs that came out of one
+// bf16x2 convert, so everything but the logs is a packed f32 operation.
+//
+// Contraction is off and every fused multiply-add is spelled out: which
+// product of a sum the compiler fuses changes the last bit, and it
+// chose differently from one instantiation (and one loop copy) to the
+// next.  The forms below are the ones all six instantiations had when
+// the kernel was first measured and tested:
+//   sq   = fma(z[P-1], z[P-1], ... fma(z0, z0, z1 * z1))
+//   var  = fma(sq, 1/P, -(mean * mean)),  mean = sum * (1/P)
+//   out  = fma(-sum, 1/P, z) * inv        (= (z - mean) * inv exactly)
+template <int P, bool CLAMP>
+__device__ __forceinline__ void normalize_task(const f32x4 (&rq)[P],
+                                               bool live,
+                                               nbf16x4 (&zo)[P]) {
+    #pragma clang fp contract(off)
+    const f32x2 rP = (f32x2)(1.0f / (float)P);
+    #pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        f32x2 z[P];
+        #pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const f32x2 r2 = {rq[p][2 * h], rq[p][2 * h + 1]};
+            f32x2 num = 1.0f + r2;
+            f32x2 den = 1.0f - r2;
+            if constexpr (CLAMP) {
+                num[0] = __builtin_fmaxf(num[0], 1e-4f);
+                num[1] = __builtin_fmaxf(num[1], 1e-4f);
+                den[0] = __builtin_fmaxf(den[0], 1e-4f);
+                den[1] = __builtin_fmaxf(den[1], 1e-4f);
+            }
+            const f32x2 ln = {__builtin_amdgcn_logf(num[0]),
+                              __builtin_amdgcn_logf(num[1])};
+            const f32x2 ld = {__builtin_amdgcn_logf(den[0]),
+                              __builtin_amdgcn_logf(den[1])};
+            z[p] = ln - ld;
+        }
+        f32x2 sum = (f32x2)0.f + z[0];
+        f32x2 sq = __builtin_elementwise_fma(z[0], z[0], z[1] * z[1]);
+        sum += z[1];
+        #pragma unroll
+        for (int p = 2; p < P; ++p) {
+            sum += z[p];
+            sq = __builtin_elementwise_fma(z[p], z[p], sq);
+        }
+        const f32x2 mean = sum * rP;
+        const f32x2 var = __builtin_elementwise_fma(sq, rP, -(mean * mean));
+        f32x2 inv;
+        #pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            inv[j] = (var[j] <= 0.f) ? 0.f : __builtin_amdgcn_rsqf(var[j]);
+            if (!live) inv[j] = 0.f;
+        }
+        #pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const f32x2 o = __builtin_elementwise_fma(-sum, rP, z[p]) * inv;
+            zo[p][2 * h] = (__bf16)o[0];
+            zo[p][2 * h + 1] = (__bf16)o[1];
+        }
+    }
+}
+
 template <int TP, int LP>
 __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     const bf16_t* __restrict__ T1, const bf16_t* __restrict__ T2,
     float* __restrict__ Gout, ll VA, ll VB, ll s0, ll C, int nsplit,
-    int do_shrink) {
+    int do_shrink, int force_clamp) {
     constexpr int P = TP;
     constexpr int NSUBJ = FS_E / P;
     constexpr int SPW = NSUBJ / FS_NW;           // subjects per wave
@@ -148,19 +225,29 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
             dst[p] = load_frag<LP>(col_row(s * P + p, v), q, ks);
     };
 
+    // the wave's SPW x P (x KS) selected-voxel fragments do not depend
+    // on the window: they are loaded once and stay in registers for the
+    // whole sweep (16 / 32 / 64 VGPRs for LP = 16 / 32 / 64)
+    FragT<LP> sel[SPW][P][KS];
+    #pragma unroll
+    for (int si = 0; si < SPW; ++si)
+        #pragma unroll
+        for (int p = 0; p < P; ++p)
+            #pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                sel[si][p][ks] = load_frag<LP>(
+                    sel_row((wv + FS_NW * si) * P + p), q, ks);
+
     FragT<LP> cur[P], nxt[P];
     if (w0 < w1) load_cols(w0 * FS_VT, 0, 0, 0, cur);
 
     for (ll w = w0; w < w1; ++w) {
         const ll v0 = w * FS_VT;
         unsigned char* zimg = zbuf[(w - w0) & 1];
-        #pragma unroll 1
+        // fully unrolled (SPW is 2 or 4) so that sel indexes statically
+        #pragma unroll
         for (int si = 0; si < SPW; ++si) {
             const int s = wv + FS_NW * si;
-            FragT<LP> sel[P];
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                sel[p] = load_frag<LP>(sel_row(s * P + p), q, 0);
             #pragma unroll
             for (int st = 0; st < 2; ++st) {
                 // issue the next task's column loads before this
@@ -174,16 +261,14 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
                 f32x4 r[P];
                 #pragma unroll
                 for (int p = 0; p < P; ++p)
-                    r[p] = corr_mfma<LP>(cur[p], sel[p], (f32x4)0.f);
+                    r[p] = corr_mfma<LP>(cur[p], sel[si][p][0], (f32x4)0.f);
                 if constexpr (KS == 2) {
                     FragT<LP> c2[P];
                     load_cols(v0, si, st, 1, c2);
                     #pragma unroll
-                    for (int p = 0; p < P; ++p) {
-                        FragT<LP> b2 =
-                            load_frag<LP>(sel_row(s * P + p), q, 1);
-                        r[p] = corr_mfma<LP>(c2[p], b2, r[p]);
-                    }
+                    for (int p = 0; p < P; ++p)
+                        r[p] = corr_mfma<LP>(c2[p], sel[si][p][KS - 1],
+                                             r[p]);
                 }
                 // r goes through bf16: same quantisation points as the
                 // raw-correlation tensor of the streamed path.  Two
@@ -200,24 +285,26 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
                         rq[p][2 * h + 1] =
                             __builtin_bit_cast(float, u & 0xffff0000u);
                     }
-                nbf16x4 zo[P];
+                // clamp on demand: |rq| >= 1 (the diagonal of a self-
+                // correlation, duplicated voxels) is the only case in
+                // which the clamp of the Fisher z changes anything.
+                // One running max per lane, one ballot per task: the
+                // whole wave runs one version.  Dead sub-tiles go
+                // through the same test (their z is forced to 0).
+                float amax = 0.f;
                 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float z[P];
-                    float mean = 0.f, sq = 0.f;
-                    #pragma unroll
-                    for (int p = 0; p < P; ++p) {
-                        z[p] = fisher_z_unscaled_bf16r(rq[p][i]);
-                        mean += z[p]; sq += z[p] * z[p];
-                    }
-                    mean /= (float)P;
-                    float var = sq / (float)P - mean * mean;
-                    float inv = (var <= 0.f) ? 0.f : __builtin_amdgcn_rsqf(var);
-                    if (!live) inv = 0.f;
-                    #pragma unroll
-                    for (int p = 0; p < P; ++p)
-                        zo[p][i] = (__bf16)((z[p] - mean) * inv);
+                for (int p = 0; p < P; ++p) {
+                    amax = __builtin_fmaxf(__builtin_fmaxf(amax,
+                        __builtin_fabsf(rq[p][0])), __builtin_fabsf(rq[p][1]));
+                    amax = __builtin_fmaxf(__builtin_fmaxf(amax,
+                        __builtin_fabsf(rq[p][2])), __builtin_fabsf(rq[p][3]));
                 }
+                nbf16x4 zo[P];
+                if (force_clamp
+                    || __builtin_amdgcn_ballot_w64(!(amax < 1.0f)) != 0)
+                    normalize_task<P, true>(rq, live, zo);
+                else
+                    normalize_task<P, false>(rq, live, zo);
                 // 8-byte store: columns st*16 + 4q .. +3 of row (c, e)
                 const int chunk = st * 2 + (q >> 1);
                 #pragma unroll
@@ -306,14 +393,15 @@ extern "C" int fcma_corr_gram_fused_vt(void) { return FS_VT; }
 
 extern "C" void launch_fcma_corr_gram_fused(
     const void* T1, const void* T2, float* Gout, int LP, ll VA, ll VB,
-    ll s0, ll C, int P, int nsplit, int do_shrink, hipStream_t stream) {
+    ll s0, ll C, int P, int nsplit, int do_shrink, int force_clamp,
+    hipStream_t stream) {
     ll grid = ((C + FS_CB - 1) / FS_CB) * nsplit;
     #define FS_ONE(TP, TLP)                                              \
         hipLaunchKernelGGL((k_corr_gram_fused<TP, TLP>), dim3(grid),     \
                            dim3(64 * FS_NW), 0, stream,                  \
                            (const bf16_t*)T1,                            \
                            (const bf16_t*)T2, Gout, VA, VB, s0, C,       \
-                           nsplit, do_shrink)
+                           nsplit, do_shrink, force_clamp)
     if (P == 4) {
         switch (LP) {
             case 16: FS_ONE(4, 16); return;
