@@ -10,6 +10,7 @@ for exact reference parity.
 """
 
 import multiprocessing
+import os
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -142,16 +143,22 @@ class FoldPlan:
 
 
 def svm_cv_device(kernels: torch.Tensor, plan: FoldPlan, C: float,
-                  tol: float) -> torch.Tensor:
+                  tol: float, variant: Optional[str] = None
+                  ) -> torch.Tensor:
     """Batched-SMO CV on the CURRENT stream, returning the per-voxel
     mean accuracy as a DEVICE tensor — no host sync, so it can be
-    enqueued on a side stream while the duo sweep continues."""
+    enqueued on a side stream while the duo sweep continues.
+
+    ``variant`` selects the ``ops.svm_cv`` kernel ("auto", "shared" or
+    "wave"); None takes it from BRAINIAK_SVM_CV, default "auto"."""
     from .. import ops
+    if variant is None:
+        variant = os.environ.get("BRAINIAK_SVM_CV", "auto")
     correct = ops.svm_cv(
         kernels.to(torch.float32).contiguous(),
         plan.y, plan.train_idx, plan.test_idx,
         plan.n_train, plan.n_test, C=C, tol=tol,
-        max_n=plan.max_n)
+        max_n=plan.max_n, variant=variant)
     return (correct.to(torch.float32) / plan.n_test_f).mean(dim=1)
 
 

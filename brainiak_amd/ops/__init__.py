@@ -232,17 +232,25 @@ def isfc_fused_(acc: torch.Tensor, Zs: torch.Tensor,
 
 def svm_cv(kernels: torch.Tensor, y: torch.Tensor, train_idx, test_idx,
            n_train, n_test, C: float = 1.0, tol: float = 1e-3,
-           max_iter: int = 10000, max_n: int = -1) -> torch.Tensor:
+           max_iter: int = 10000, max_n: int = -1,
+           variant: str = "auto") -> torch.Tensor:
     """Batched precomputed-kernel SVC k-fold CV fully on device.
 
     One wavefront per (voxel, fold) dual QP (SMO, WSS1); returns
-    correct-prediction counts [C, F] int32.  n_train/n_test <= 64.
+    correct-prediction counts [C, F] int32.  n_train/n_test <= 128.
     max_n > 0 skips the fold-size .item() sync (pass
     max(n_train.max(), n_test.max()) computed on the host) so the
     launch can be enqueued on a side stream without draining it.
+
+    variant: ``"shared"`` runs one workgroup per voxel whose fold-waves
+    share one staged [E, E] tile (E <= 128 and the tile within 64 KB of
+    LDS; raises otherwise), ``"wave"`` one single-wave workgroup per
+    (voxel, fold) with its own Q tile, ``"auto"`` the shared kernel
+    wherever it fits.  The two give identical counts.
     """
     return _ext().svm_cv(kernels, y, train_idx, test_idx, n_train, n_test,
-                         float(C), float(tol), int(max_iter), int(max_n))
+                         float(C), float(tol), int(max_iter), int(max_n),
+                         str(variant))
 
 
 def jacobi_eigh(G: torch.Tensor):

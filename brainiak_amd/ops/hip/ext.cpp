@@ -44,7 +44,8 @@ void launch_tfa_recon(const float*, const float*, const float*, float*,
                       ll, ll, int, float, void*);
 void launch_svm_cv(const float*, const float*, const int*, const int*,
                    const int*, const int*, int*, ll, int, int, float,
-                   float, int, ll, void*);
+                   float, int, ll, int, void*);
+int svm_cv_shared_fits(int, ll);
 ll fcma_supported_L(ll);
 int fcma_corr_norm_smem(ll, int);
 int fcma_fused_gram_supported(ll, int, ll);
@@ -556,7 +557,7 @@ torch::Tensor svm_cv(torch::Tensor kernels, torch::Tensor y,
                      torch::Tensor train_idx, torch::Tensor test_idx,
                      torch::Tensor n_train, torch::Tensor n_test,
                      double Creg, double tol, int64_t max_iter,
-                     int64_t max_n_hint) {
+                     int64_t max_n_hint, const std::string& variant) {
     check_3d(kernels, torch::kFloat32, "kernels");
     ll C = kernels.size(0);
     int E = (int)kernels.size(1);
@@ -577,13 +578,26 @@ torch::Tensor svm_cv(torch::Tensor kernels, torch::Tensor y,
         : std::max<ll>(nt.max().item<int>(), ns.max().item<int>());
     TORCH_CHECK(max_n <= 128,
                 "svm_cv supports fold sizes up to 128 samples");
+    // "shared": one workgroup per voxel, the folds share one K tile;
+    // "wave": one wave per (voxel, fold) QP; "auto": shared when its
+    // tile fits.  Both give the same counts.
+    TORCH_CHECK(variant == "auto" || variant == "shared" ||
+                variant == "wave",
+                "variant must be \"auto\", \"shared\" or \"wave\"");
+    TORCH_CHECK(variant != "shared" || svm_cv_shared_fits(E, max_n),
+                "svm_cv variant \"shared\" needs E <= 128 and an [E,E] "
+                "tile within 64 KB of LDS; got E=", E, ", fold size ",
+                max_n);
+    const int variant_id = variant == "shared" ? 1
+                         : variant == "wave" ? 2 : 0;
     auto correct = torch::zeros({C, F}, kernels.options()
                                             .dtype(torch::kInt32));
     launch_svm_cv(kernels.data_ptr<float>(), y.data_ptr<float>(),
                   train_idx.data_ptr<int>(), test_idx.data_ptr<int>(),
                   nt.data_ptr<int>(), ns.data_ptr<int>(),
                   correct.data_ptr<int>(), C, E, F, (float)Creg,
-                  (float)tol, (int)max_iter, max_n, cur_stream());
+                  (float)tol, (int)max_iter, max_n, variant_id,
+                  cur_stream());
     return correct;
 }
 
@@ -908,7 +922,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "acc += atanh(sym(Zs_b Zm_b^T)) per subject, M never "
           "materialized (bf16 MFMA tile pairs)");
     m.def("svm_cv", &svm_cv,
-          "batched precomputed-kernel SVC cross-validation");
+          "batched precomputed-kernel SVC cross-validation",
+          py::arg("kernels"), py::arg("y"), py::arg("train_idx"),
+          py::arg("test_idx"), py::arg("n_train"), py::arg("n_test"),
+          py::arg("C"), py::arg("tol"), py::arg("max_iter"),
+          py::arg("max_n") = -1, py::arg("variant") = "auto");
+    m.def("svm_cv_shared_fits",
+          [](int64_t E, int64_t max_n) {
+              return svm_cv_shared_fits((int)E, (ll)max_n) != 0;
+          },
+          "true when the shared-tile svm_cv variant covers the shape");
     m.def("fcma_normalize_", &fcma_normalize_,
           "in-place Fisher-z + within-subject z-score [C,E,V]");
     m.def("fcma_correlate", &fcma_correlate,

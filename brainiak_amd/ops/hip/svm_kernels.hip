@@ -2,12 +2,18 @@
 //
 // The reference scores each voxel's [E,E] kernel with sklearn SVC in a CPU
 // process pool (ref src/brainiak/fcma/voxelselector.py:423-465).  Here ONE
-// kernel launch solves every (voxel, fold) dual QP: one workgroup (64
-// threads = 1 wave) per problem, Q staged in LDS, SMO with
-// maximal-violating-pair selection (LIBSVM WSS1), then the fold's test
-// accuracy computed in the same block.  VPL dual variables per lane
-// (variable v = k*64 + lane): VPL=1 covers n_train <= 64, VPL=2 covers
-// n_train <= 128 (Q tile 66 KB LDS, dynamic).
+// kernel launch solves every (voxel, fold) dual QP, one wave per problem:
+// SMO with maximal-violating-pair selection (LIBSVM WSS1), then the
+// fold's test accuracy computed by the same wave.  VPL dual variables
+// per lane: VPL=1 covers n_train <= 64, VPL=2 covers n_train <= 128
+// (fp16 tile).
+//
+// Two kernels, identical counts:
+//  - k_svm_cv: one single-wave workgroup per (voxel, fold), its own
+//    signed Q tile in LDS (variable v = k*64 + lane).  Fallback for
+//    E > 128 and the yardstick the shared kernel is tested against.
+//  - k_svm_cv_shared (further down): one workgroup per voxel, the folds'
+//    waves share one staged K tile.  The default wherever it fits.
 //
 // Output: correct-prediction counts [C, F] int32; host divides by test
 // counts and averages folds.
@@ -174,12 +180,311 @@ __global__ __launch_bounds__(64) void k_svm_cv(
     if (lane == 0) correct[c * F + f] = correct_local;
 }
 
+// ---------------------------------------------------------------------------
+// Shared-tile variant: one workgroup per VOXEL, one wave per fold.
+//
+// The four (F) folds of a voxel solve QPs over sub-matrices of the same
+// [E,E] kernel, so the block stages K once (row stride S = E|1, fp32 for
+// VPL=1, fp16 for VPL=2) and every fold-wave reads it:
+// Q[i][v] = (y_i y_v) K[tr_i][tr_v], the +-1 sign applied on the fly
+// (exact, and it commutes with the fp16 rounding, so the values are the
+// ones k_svm_cv stores).  After the staging barrier the waves never meet
+// again: a QP is one wave, its trip count is its own, and there is NO
+// block barrier below that line.
+//
+// An SMO iteration touches LDS once (the two Q rows, independent reads):
+//  - lane l owns variable bitrev6(l) (+64 for the second one), so that
+//    "first set bit of the (score == best) ballot" is exactly the winner
+//    of k_svm_cv's strict-compare xor butterfly as lane 0 sees it (the
+//    tied lane with the smallest bit-reversed index; a lane's k=0
+//    candidate beats its k=1 on ties).  The value itself is reduced with
+//    DPP max/min and then re-read from the winning lane, so a -0/+0 tie
+//    returns the winner's zero as the butterfly does.
+//  - every lane computes the step from v_readlane of the pair's y,
+//    alpha, row offset and diagonal; Q_ij is lane j's element of row i.
+//
+// The arithmetic forms are those k_svm_cv compiles to (contraction is off
+// here and each fma is spelled out), so the two variants give the same
+// trajectory bit for bit: eta = fma(-y_j, y_i*(Q_ij+Q_ij), Q_ii+Q_jj);
+// correctly rounded division; grad + (Q_iv*da_i + Q_jv*da_j) unfused,
+// except the FIRST variable of a two-variable lane, which k_svm_cv<2>
+// contracts to grad + fma(Q_iv, da_i, Q_jv*da_j).
+
+// order-preserving float <-> int32 key (its own inverse): the reduction
+// runs on integers, so the DPP operand folds into v_max_i32/v_min_i32
+// and no NaN-quieting canonicalisation sits between the steps.  Scores
+// are never NaN here (a candidate passed an ordered compare), and -0
+// and +0 get adjacent keys, which the float == ballot treats as a tie.
+__device__ __forceinline__ int float_key(int bits) {
+    return bits ^ ((bits >> 31) & 0x7fffffff);
+}
+
+template <bool IS_MAX>
+__device__ __forceinline__ float wave_reduce_dpp(float xf) {
+    // quad xor 1, quad xor 2, half-row mirror, row mirror, then the two
+    // row broadcasts: lane 63 ends up holding the wave's max/min
+    int x = float_key(__float_as_int(xf));
+#define SVM_DPP_STEP(ctrl, row_mask)                                        \
+    {                                                                       \
+        int o = __builtin_amdgcn_update_dpp(                                \
+            IS_MAX ? (int)0x80000000 : 0x7fffffff, x, ctrl, row_mask, 0xf,  \
+            false);  /* rows masked off see the identity */                 \
+        x = IS_MAX ? max(x, o) : min(x, o);                                 \
+    }
+    SVM_DPP_STEP(0xB1, 0xf)    // quad_perm [1,0,3,2]
+    SVM_DPP_STEP(0x4E, 0xf)    // quad_perm [2,3,0,1]
+    SVM_DPP_STEP(0x141, 0xf)   // row_half_mirror
+    SVM_DPP_STEP(0x140, 0xf)   // row_mirror
+    SVM_DPP_STEP(0x142, 0xa)   // row_bcast:15 into rows 1, 3
+    SVM_DPP_STEP(0x143, 0xc)   // row_bcast:31 into rows 2, 3
+#undef SVM_DPP_STEP
+    return __int_as_float(float_key(__builtin_amdgcn_readlane(x, 63)));
+}
+
+__device__ __forceinline__ float lane_f(float x, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
+}
+
+__device__ __forceinline__ int first_lane(unsigned long long m) {
+    return m ? (int)__ffsll((long long)m) - 1 : 0;
+}
+
+template <int VPL>
+__global__ __launch_bounds__(512) void k_svm_cv_shared(
+    const float* __restrict__ kernels,  // [C, E, E]
+    const float* __restrict__ y,        // [E] in {-1, +1}
+    const int* __restrict__ train_idx,  // [F, E] (first n_train valid)
+    const int* __restrict__ test_idx,   // [F, E] (first n_test valid)
+    const int* __restrict__ n_train,    // [F]
+    const int* __restrict__ n_test,     // [F]
+    int* __restrict__ correct,          // [C, F]
+    ll C, int E, int F, int S, float Creg, float tol, int max_iter) {
+    #pragma clang fp contract(off)
+    using QT = typename std::conditional<VPL == 1, float, _Float16>::type;
+    extern __shared__ char smem_raw[];
+    QT* tile = (QT*)smem_raw;           // [E][S], K as given (no sign)
+
+    const ll c = blockIdx.x;
+    if (c >= C) return;                 // whole block: before the barrier
+    const float* Kc = kernels + c * (ll)E * E;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int EE = E * E;
+
+    // stage K once for all folds: 16-byte coalesced loads when the
+    // voxel's matrix is 16-byte aligned (E even and an aligned base)
+    int done = 0;
+    if ((((uintptr_t)Kc) & 15) == 0) {
+        const int nvec = EE >> 2;
+        for (int q = tid; q < nvec; q += nthr) {
+            const float4 v4 = ((const float4*)Kc)[q];
+            const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+            int r = (q * 4) / E;
+            int cc = q * 4 - r * E;
+            #pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                tile[r * S + cc] = (QT)vv[u];
+                if (++cc == E) { cc = 0; ++r; }
+            }
+        }
+        done = nvec << 2;
+    }
+    for (int e = done + tid; e < EE; e += nthr) {
+        int r = e / E;
+        tile[r * S + (e - r * E)] = (QT)Kc[e];
+    }
+    __syncthreads();
+    // ---- no block-level barrier from here on ----
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nwave = nthr >> 6;
+    const int lane = tid & 63;
+    const int vb = (int)(__brev((unsigned)lane) >> 26);   // bitrev6(lane)
+    const float cup = Creg - 1e-12f;
+
+    for (int f = wave; f < F; f += nwave) {
+        const int n = n_train[f];
+        const int m = n_test[f];
+        const int* tr = train_idx + (ll)f * E;
+        const int* te = test_idx + (ll)f * E;
+
+        // lane-private variables: v = k*64 + bitrev6(lane)
+        bool valid[VPL];
+        int col[VPL];                   // tr[v]: column (and row) in K
+        float yl[VPL], qd[VPL], alpha[VPL], grad[VPL];
+        #pragma unroll
+        for (int k = 0; k < VPL; ++k) {
+            int v = k * 64 + vb;
+            valid[k] = v < n;
+            col[k] = valid[k] ? tr[v] : 0;
+            yl[k] = valid[k] ? y[col[k]] : 0.0f;
+            qd[k] = (float)tile[col[k] * S + col[k]];   // Q_vv = K_vv
+            alpha[k] = 0.0f;
+            grad[k] = -1.0f;
+        }
+
+        float b = 0.0f;
+        for (int iter = 0; iter < max_iter; ++iter) {
+            // per-lane best over its VPL variables (k=0 wins ties)
+            float uv = -3.0e38f, lv = 3.0e38f;
+            int ku = 0, kl = 0;
+            #pragma unroll
+            for (int k = 0; k < VPL; ++k) {
+                float score = -yl[k] * grad[k];
+                bool in_up = valid[k] &&
+                    ((yl[k] > 0.f && alpha[k] < cup) ||
+                     (yl[k] < 0.f && alpha[k] > 1e-12f));
+                bool in_low = valid[k] &&
+                    ((yl[k] > 0.f && alpha[k] > 1e-12f) ||
+                     (yl[k] < 0.f && alpha[k] < cup));
+                if (in_up && score > uv) { uv = score; ku = k; }
+                if (in_low && score < lv) { lv = score; kl = k; }
+            }
+            // value by DPP, index = first lane holding it (bit-reversed
+            // layout => the butterfly's winner); no candidate anywhere
+            // leaves every lane at the sentinel and picks variable 0
+            const float ubest = wave_reduce_dpp<true>(uv);
+            const float lbest = wave_reduce_dpp<false>(lv);
+            const int li = first_lane(__ballot(uv == ubest));
+            const int lj = first_lane(__ballot(lv == lbest));
+            const float up = lane_f(uv, li);
+            const float lo = lane_f(lv, lj);
+            const float gap = __fsub_rn(up, lo);
+            b = __fmul_rn(0.5f, __fadd_rn(up, lo));
+            if (gap < tol) break;
+
+            // each lane's own candidate, then the pair's via readlane
+            float yu = yl[0], au = alpha[0], du = qd[0];
+            float ylo = yl[0], alo = alpha[0], dlo = qd[0];
+            int cu = col[0], clo = col[0];
+            if (VPL == 2) {
+                if (ku) { yu = yl[VPL - 1]; au = alpha[VPL - 1];
+                          du = qd[VPL - 1]; cu = col[VPL - 1]; }
+                if (kl) { ylo = yl[VPL - 1]; alo = alpha[VPL - 1];
+                          dlo = qd[VPL - 1]; clo = col[VPL - 1]; }
+            }
+            const float yi = lane_f(yu, li), yj = lane_f(ylo, lj);
+            const float ai = lane_f(au, li), aj = lane_f(alo, lj);
+            const float Qii = lane_f(du, li), Qjj = lane_f(dlo, lj);
+            const int ri = __builtin_amdgcn_readlane(cu, li) * S;
+            const int rj = __builtin_amdgcn_readlane(clo, lj) * S;
+            const int ki = __builtin_amdgcn_readlane(ku, li);
+            const int kj = __builtin_amdgcn_readlane(kl, lj);
+
+            // the iteration's only LDS traffic: rows i and j
+            float qi[VPL], qj[VPL];
+            #pragma unroll
+            for (int k = 0; k < VPL; ++k) {
+                float a = (float)tile[ri + col[k]];
+                float bq = (float)tile[rj + col[k]];
+                qi[k] = __fmul_rn(__fmul_rn(yi, yl[k]), a);
+                qj[k] = __fmul_rn(__fmul_rn(yj, yl[k]), bq);
+            }
+            float qsel = qi[0];
+            if (VPL == 2 && kl) qsel = qi[VPL - 1];
+            const float Qij = lane_f(qsel, lj);
+
+            float eta = fmaf(-yj, __fmul_rn(yi, __fadd_rn(Qij, Qij)),
+                             __fadd_rn(Qii, Qjj));
+            eta = fmaxf(eta, 1e-12f);
+            float t = __fdiv_rn(gap, eta);
+            float tmax_i = (yi > 0.f) ? __fsub_rn(Creg, ai) : ai;
+            float tmax_j = (yj > 0.f) ? aj : __fsub_rn(Creg, aj);
+            t = fminf(t, fminf(tmax_i, tmax_j));
+            t = fmaxf(t, 0.0f);
+            const float dai = __fmul_rn(yi, t);      // d alpha_i
+            const float daj = __fmul_rn(-yj, t);     // d alpha_j
+
+            #pragma unroll
+            for (int k = 0; k < VPL; ++k) {
+                if (lane == li && k == ki) alpha[k] = __fadd_rn(alpha[k], dai);
+                if (lane == lj && k == kj) alpha[k] = __fadd_rn(alpha[k], daj);
+                float d;
+                if (VPL == 2 && k == 0)
+                    d = fmaf(qi[k], dai, __fmul_rn(qj[k], daj));
+                else
+                    d = __fadd_rn(__fmul_rn(qi[k], dai),
+                                  __fmul_rn(qj[k], daj));
+                if (valid[k]) grad[k] = __fadd_rn(grad[k], d);
+            }
+        }
+
+        // predict the fold's test samples: the sequential fmaf chain
+        // over variables 0..n-1, coefficients and columns by readlane.
+        // All lanes walk the chain (idle ones on row 0) so the readlane
+        // sources stay active.  VPL=1 reads K from the tile; the fp16
+        // tile of VPL=2 is not what k_svm_cv predicts with, so that
+        // instance reads the fp32 matrix from global memory as it does.
+        float coef[VPL];
+        #pragma unroll
+        for (int k = 0; k < VPL; ++k)
+            coef[k] = __fmul_rn(alpha[k], yl[k]);   // coef_i = alpha_i y_i
+        int correct_w = 0;
+        #pragma unroll
+        for (int k = 0; k < VPL; ++k) {
+            if (k * 64 >= m) break;
+            const int tv = k * 64 + lane;
+            const bool act = tv < m;
+            const int trow = act ? te[tv] : 0;
+            const float yt = y[trow];
+            float dec = b;
+            #pragma unroll
+            for (int kk = 0; kk < VPL; ++kk) {
+                const int cnt = min(64, n - kk * 64);
+                for (int i = 0; i < cnt; ++i) {
+                    const int src = (int)(__brev((unsigned)i) >> 26);
+                    const float cf = lane_f(coef[kk], src);
+                    const int ci = __builtin_amdgcn_readlane(col[kk], src);
+                    float kv;
+                    if (VPL == 1) kv = (float)tile[trow * S + ci];
+                    else          kv = Kc[(ll)trow * E + ci];
+                    dec = fmaf(cf, kv, dec);
+                }
+            }
+            correct_w += __popcll(__ballot(
+                act && ((dec > 0.f) == (yt > 0.f))));
+        }
+        if (lane == 0) correct[c * F + f] = correct_w;
+    }
+}
+
+// tile bytes of the shared variant, or 0 when the shape is not covered.
+// The tile is the whole [E, E] matrix (k_svm_cv stages only a fold's
+// [n, n] part) and must fit the 64 KB dynamic-LDS launch limit.  E is
+// capped at 128, the range the equality tests cover; an fp16 tile of a
+// larger E could still fit, but those shapes stay on k_svm_cv.
+static size_t svm_cv_shared_smem(int E, ll max_n) {
+    if (E < 1 || E > 128 || max_n < 1 || max_n > 128) return 0;
+    size_t bytes = (size_t)E * (size_t)(E | 1) * (max_n <= 64 ? 4 : 2);
+    return bytes <= 65536 ? bytes : 0;
+}
+
+extern "C" int svm_cv_shared_fits(int E, ll max_n) {
+    return svm_cv_shared_smem(E, max_n) != 0;
+}
+
+// variant: 0 = auto (shared when it fits), 1 = shared, 2 = one wave per QP
 extern "C" void launch_svm_cv(const float* kernels, const float* y,
                               const int* train_idx, const int* test_idx,
                               const int* n_train, const int* n_test,
                               int* correct, ll C, int E, int F, float Creg,
                               float tol, int max_iter, ll max_n,
-                              hipStream_t stream) {
+                              int variant, hipStream_t stream) {
+    const size_t shared_smem = svm_cv_shared_smem(E, max_n);
+    if (variant != 2 && shared_smem != 0) {
+        const int W = F < 8 ? F : 8;
+        const int S = E | 1;
+        if (max_n <= 64)
+            hipLaunchKernelGGL(k_svm_cv_shared<1>, dim3((unsigned)C),
+                               dim3(64 * W), shared_smem, stream, kernels,
+                               y, train_idx, test_idx, n_train, n_test,
+                               correct, C, E, F, S, Creg, tol, max_iter);
+        else
+            hipLaunchKernelGGL(k_svm_cv_shared<2>, dim3((unsigned)C),
+                               dim3(64 * W), shared_smem, stream, kernels,
+                               y, train_idx, test_idx, n_train, n_test,
+                               correct, C, E, F, S, Creg, tol, max_iter);
+        return;
+    }
     if (max_n <= 64) {
         size_t smem = (size_t)64 * 65 * 4 + 2 * 64 * 4;
         hipLaunchKernelGGL(k_svm_cv<1>, dim3((unsigned)(C * F)), dim3(64),
