@@ -375,7 +375,10 @@ class CorrelationPipeline:
         consecutive chunks merge into super-chunks of at least one
         workgroup per CU, one ``fcma_corr_gram_fused`` launch each, and
         the per-chunk views of its result go to the consumer in chunk
-        order on the current stream."""
+        order on the current stream.
+        BRAINIAK_FCMA_SCHED=phased (or ahead) picks the kernel's
+        schedule; the results do not depend on it."""
+        sched = os.environ.get("BRAINIAK_FCMA_SCHED", "") or "auto"
         a_t, b_t = self._fused_operands()
         E = self.num_epochs
         P = self.epochs_per_subj
@@ -397,7 +400,8 @@ class CorrelationPipeline:
             blocks = (total + cb - 1) // cb
             nsplit = max(1, min((wave // cb) // blocks, windows))
             g = ops.fcma_corr_gram_fused(a_t, b_t, start, total, P,
-                                         nsplit=nsplit, shrink=shrink)
+                                         nsplit=nsplit, shrink=shrink,
+                                         schedule=sched)
             k0 = 0
             for s_k, c_k in chunks[i:j]:
                 gk = g[k0:k0 + c_k]

@@ -203,7 +203,8 @@ def fcma_fused_operand(data: torch.Tensor) -> torch.Tensor:
 def fcma_corr_gram_fused(At_all: torch.Tensor, B_t: torch.Tensor,
                          start: int, count: int, epochs_per_subj: int,
                          nsplit: int = 1, shrink: bool = True,
-                         clamp: str = "auto") -> torch.Tensor:
+                         clamp: str = "auto",
+                         schedule: str = "auto") -> torch.Tensor:
     """Correlation + normalize + Gram in one kernel over the operands of
     ``fcma_fused_operand``: [count, 64, 64] fp32 Grams of selected voxels
     [start, start+count) of At_all against every column of B_t, with the
@@ -212,10 +213,25 @@ def fcma_corr_gram_fused(At_all: torch.Tensor, B_t: torch.Tensor,
     The operands must be finite (``stack_epochs`` zero-pads, callers
     z-score with a clamped std).  ``clamp="auto"`` applies the Fisher-z
     clamp only where a correlation reaches |r| >= 1; ``clamp="always"``
-    applies it to every element.  Both give the same bits."""
+    applies it to every element.  Both give the same bits.
+
+    ``schedule="ahead"`` issues each task's correlation MFMAs one task
+    before its normalize, with the column prefetch two tasks deep;
+    ``"phased"`` issues them at the head of the task itself, the order
+    the kernel was first shipped with; ``"auto"`` (the default) is
+    ``"ahead"``.  Epoch lengths above 32 have no ``"ahead"`` form
+    (``fcma_corr_gram_fused_ahead``) and run phased whatever is asked.
+    All give the same bits."""
     return _ext().fcma_corr_gram_fused(At_all, B_t, int(start), int(count),
                                        int(epochs_per_subj), int(nsplit),
-                                       bool(shrink), str(clamp))
+                                       bool(shrink), str(clamp),
+                                       str(schedule))
+
+
+def fcma_corr_gram_fused_ahead(P: int, L: int) -> bool:
+    """True when the ``fcma_corr_gram_fused`` instance for P epochs per
+    subject and epoch length L has the ``"ahead"`` schedule."""
+    return bool(_ext().fcma_corr_gram_fused_ahead(int(P), int(L)))
 
 
 # ---------------------------------------------------------------------------

@@ -60,8 +60,10 @@ int fcma_corr_gram_fused_supported(ll, int, ll);
 int fcma_corr_gram_fused_lp(ll);
 int fcma_corr_gram_fused_cb(void);
 int fcma_corr_gram_fused_vt(void);
+int fcma_corr_gram_fused_ahead(int, ll);
 void launch_fcma_corr_gram_fused(const void*, const void*, float*, int, ll,
-                                 ll, ll, ll, int, int, int, int, void*);
+                                 ll, ll, ll, int, int, int, int, int,
+                                 void*);
 void launch_fcma_gsum(const float*, float*, ll, ll, ll, int, void*);
 void launch_hmm_fb(const double*, const double*, const double*,
                    const double*, const double*, const int*, const int*,
@@ -415,10 +417,18 @@ torch::Tensor fcma_fused_gram(torch::Tensor A, torch::Tensor B,
 // column sweep into ranges whose partials gsum reduces in fixed order.
 // clamp = "auto" clamps the Fisher z only in tasks that hold an |r| >= 1;
 // "always" clamps every element (same bits for finite operands).
-torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
-                                   int64_t start, int64_t count, int64_t P,
-                                   int64_t nsplit, bool shrink,
-                                   const std::string& clamp) {
+// schedule = "ahead" issues each task's correlation MFMAs one task before
+// its normalize (column prefetch two tasks deep), "phased" at the head of
+// the task itself (the order the kernel was first shipped with); "auto"
+// is "ahead".  The LP = 64 instances have no "ahead" form and run phased
+// either way.  All give the same bits.
+// partials = true returns the [nsplit, count, 64, 64] slabs as the kernel
+// wrote them (unshrunk, not summed); a split without a column window
+// is an all-zero slab.
+static torch::Tensor fcma_corr_gram_fused_impl(
+    torch::Tensor At_all, torch::Tensor B_t, int64_t start, int64_t count,
+    int64_t P, int64_t nsplit, bool shrink, const std::string& clamp,
+    const std::string& schedule, bool partials) {
     check_3d(At_all, torch::kBFloat16, "At_all");
     check_3d(B_t, torch::kBFloat16, "B_t");
     ll VA = At_all.size(1), VB = B_t.size(1), LP = At_all.size(2);
@@ -436,18 +446,42 @@ torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
                 "voxel range");
     ll windows = (VB + fcma_corr_gram_fused_vt() - 1)
         / fcma_corr_gram_fused_vt();
-    TORCH_CHECK(nsplit >= 1 && nsplit <= windows,
-                "nsplit must be in [1, column windows]");
+    // The Gram entry point takes at most one split per window.  The slab
+    // view takes up to twice that: it exists to show splits without a
+    // window (all-zero slabs), and with few windows those only arise
+    // past that limit (two windows cut three ways).
+    if (partials) {
+        TORCH_CHECK(nsplit >= 1 && nsplit <= 2 * windows,
+                    "nsplit must be in [1, 2 x column windows] for the "
+                    "slab view");
+    } else {
+        TORCH_CHECK(nsplit >= 1 && nsplit <= windows,
+                    "nsplit must be in [1, column windows]");
+    }
     TORCH_CHECK(clamp == "auto" || clamp == "always",
                 "clamp must be \"auto\" or \"always\"");
     const int force_clamp = clamp == "always" ? 1 : 0;
+    TORCH_CHECK(schedule == "auto" || schedule == "ahead"
+                || schedule == "phased",
+                "schedule must be \"auto\", \"ahead\" or \"phased\"");
+    // FS_SCHED_* of fcma_fused_kernels.hip
+    const int sched = schedule == "auto" ? 0
+        : (schedule == "ahead" ? 1 : 2);
     auto opts = At_all.options().dtype(torch::kFloat32);
+    if (partials) {
+        auto Gp = torch::empty({nsplit, count, 64, 64}, opts);
+        launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
+                                    Gp.data_ptr<float>(), (int)LP, VA, VB,
+                                    start, count, (int)P, (int)nsplit, 0,
+                                    force_clamp, sched, cur_stream());
+        return Gp;
+    }
     auto G = torch::empty({count, 64, 64}, opts);
     if (nsplit == 1) {
         launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
                                     G.data_ptr<float>(), (int)LP, VA, VB,
                                     start, count, (int)P, 1,
-                                    shrink ? 1 : 0, force_clamp,
+                                    shrink ? 1 : 0, force_clamp, sched,
                                     cur_stream());
         return G;
     }
@@ -455,10 +489,27 @@ torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
     launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
                                 Gp.data_ptr<float>(), (int)LP, VA, VB,
                                 start, count, (int)P, (int)nsplit, 0,
-                                force_clamp, cur_stream());
+                                force_clamp, sched, cur_stream());
     launch_fcma_gsum(Gp.data_ptr<float>(), G.data_ptr<float>(), count,
                      64 * 64, nsplit, shrink ? 1 : 0, cur_stream());
     return G;
+}
+
+torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
+                                   int64_t start, int64_t count, int64_t P,
+                                   int64_t nsplit, bool shrink,
+                                   const std::string& clamp,
+                                   const std::string& schedule) {
+    return fcma_corr_gram_fused_impl(At_all, B_t, start, count, P, nsplit,
+                                     shrink, clamp, schedule, false);
+}
+
+torch::Tensor fcma_corr_gram_fused_partials(
+    torch::Tensor At_all, torch::Tensor B_t, int64_t start, int64_t count,
+    int64_t P, int64_t nsplit, const std::string& clamp,
+    const std::string& schedule) {
+    return fcma_corr_gram_fused_impl(At_all, B_t, start, count, P, nsplit,
+                                     false, clamp, schedule, true);
 }
 
 bool fcma_fused_gram_native(int64_t E, int64_t P, int64_t L) {
@@ -969,7 +1020,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "[64, V, LP] operands -> [count, 64, 64]",
           py::arg("At_all"), py::arg("B_t"), py::arg("start"),
           py::arg("count"), py::arg("P"), py::arg("nsplit") = 1,
-          py::arg("shrink") = true, py::arg("clamp") = "auto");
+          py::arg("shrink") = true, py::arg("clamp") = "auto",
+          py::arg("schedule") = "auto");
+    m.def("fcma_corr_gram_fused_partials", &fcma_corr_gram_fused_partials,
+          "the [nsplit, count, 64, 64] slabs of fcma_corr_gram_fused as "
+          "the kernel writes them (unshrunk, not summed)",
+          py::arg("At_all"), py::arg("B_t"), py::arg("start"),
+          py::arg("count"), py::arg("P"), py::arg("nsplit"),
+          py::arg("clamp") = "auto", py::arg("schedule") = "auto");
+    m.def("fcma_corr_gram_fused_ahead",
+          [](int64_t P, int64_t L) {
+              return fcma_corr_gram_fused_ahead((int)P, L) != 0;
+          }, "whether the (P, L) instance has the \"ahead\" schedule");
     m.def("fcma_corr_gram_fused_supported",
           [](int64_t E, int64_t P, int64_t L) {
               return fcma_corr_gram_fused_supported(E, (int)P, L) != 0;

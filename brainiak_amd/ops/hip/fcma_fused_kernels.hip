@@ -22,7 +22,9 @@
 //           The P accumulators of a subject sit in the same lane.
 //           The wave's B fragments (its subjects' selected-voxel rows)
 //           are the same for every window: they are loaded once and
-//           stay in registers for the sweep.
+//           stay in registers for the sweep.  A task is one (subject,
+//           sub-tile) pair; in the AHEAD order (below, LP <= 32) task
+//           t+1's MFMAs are issued before task t's normalize.
 //  phase 2  per element: r -> bf16 -> fp32, Fisher z, biased mean/var
 //           over P, (z - mean) * rsq(var) (var <= 0 -> 0; var is never
 //           denormal, so the raw v_rsq_f32 equals rsqrtf bit for bit),
@@ -42,6 +44,10 @@
 // and normalize of window w+1 while its neighbours still issue MFMAs.
 // (Four waves x four voxels at two blocks per CU needs 160 accumulator
 // registers per lane and spills; eight waves x two voxels does not.)
+// LDS invariant: a wave has issued and waited for every Gram read of
+// image w before it arrives at the barrier that ends window w+1,
+// because window w+2 overwrites that image.  Here the reads sit right
+// behind the barrier of window w, ahead of every store of window w+1.
 //
 // LDS image: row (c, e) is 64 B = four 16-B chunks, chunk index XORed
 // with (e>>2)&3 so the Gram's ds_read_b128 (16 rows x one chunk per
@@ -163,7 +169,24 @@ __device__ __forceinline__ void normalize_task(const f32x4 (&rq)[P],
     }
 }
 
-template <int TP, int LP>
+// launch_fcma_corr_gram_fused's schedule argument (ext.cpp maps the
+// strings "auto" / "ahead" / "phased" to these)
+#define FS_SCHED_AUTO 0
+#define FS_SCHED_AHEAD 1
+#define FS_SCHED_PHASED 2
+
+// AHEAD: the correlation MFMAs of task t+1 are issued before the
+// normalize of task t, from column fragments loaded a whole task
+// earlier (the column prefetch runs two tasks deep).  The MFMAs then
+// never wait on their loads and their results are long there when the
+// bf16 converts want them.  One-k-step instances only (LP <= 32): the
+// second k-step of LP = 64 would need a third set of column fragments.
+// AHEAD = false is the order the kernel was first shipped with (load one
+// task ahead, MFMA at the head of its own task).  Both give the same
+// bits: the same MFMAs on the same operands.
+static constexpr bool fs_has_ahead(int LP) { return LP <= 32; }
+
+template <int TP, int LP, bool AHEAD>
 __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     const bf16_t* __restrict__ T1, const bf16_t* __restrict__ T2,
     float* __restrict__ Gout, ll VA, ll VB, ll s0, ll C, int nsplit,
@@ -172,6 +195,8 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     constexpr int NSUBJ = FS_E / P;
     constexpr int SPW = NSUBJ / FS_NW;           // subjects per wave
     constexpr int KS = (LP + 31) / 32;         // MFMA k-steps
+    constexpr int NT = 2 * SPW;                // tasks per window
+    static_assert(!AHEAD || KS == 1, "AHEAD needs a one-k-step instance");
 
     const ll vs = blockIdx.x % nsplit;
     const ll ct = blockIdx.x / nsplit;
@@ -238,8 +263,27 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
                 sel[si][p][ks] = load_frag<LP>(
                     sel_row((wv + FS_NW * si) * P + p), q, ks);
 
+    // task k = 2 * si + st of the window at v0; k >= NT runs on into
+    // the next window (past the last column load_cols clamps)
+    auto load_task = [&](ll v0, int k, FragT<LP> dst[P]) {
+        if (k >= NT) { v0 += FS_VT; k -= NT; }
+        load_cols(v0, k >> 1, k & 1, 0, dst);
+    };
+
     FragT<LP> cur[P], nxt[P];
-    if (w0 < w1) load_cols(w0 * FS_VT, 0, 0, 0, cur);
+    f32x4 rn[P];
+    if (w0 < w1) {
+        load_cols(w0 * FS_VT, 0, 0, 0, cur);
+        if constexpr (AHEAD) {
+            // cur feeds the first task's MFMAs here and is free again;
+            // from now on nxt holds the columns of the task after the
+            // current one and rn its correlations
+            load_cols(w0 * FS_VT, 0, 1, 0, nxt);
+            #pragma unroll
+            for (int p = 0; p < P; ++p)
+                rn[p] = corr_mfma<LP>(cur[p], sel[0][p][0], (f32x4)0.f);
+        }
+    }
 
     for (ll w = w0; w < w1; ++w) {
         const ll v0 = w * FS_VT;
@@ -250,18 +294,33 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
             const int s = wv + FS_NW * si;
             #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                // issue the next task's column loads before this
-                // task's MFMA + normalize: their latency hides under
-                // the VALU work
-                if (st == 0) load_cols(v0, si, 1, 0, nxt);
-                else if (si + 1 < SPW) load_cols(v0, si + 1, 0, 0, nxt);
-                else if (w + 1 < w1) load_cols(v0 + FS_VT, 0, 0, 0, nxt);
-
+                const int k = 2 * si + st;
                 const bool live = (v0 + st * 16) < VB;   // wave-uniform
                 f32x4 r[P];
-                #pragma unroll
-                for (int p = 0; p < P; ++p)
-                    r[p] = corr_mfma<LP>(cur[p], sel[si][p][0], (f32x4)0.f);
+                if constexpr (AHEAD) {
+                    // columns of task k+2 out, correlations of task
+                    // k+1 out (its columns came in during task k-1),
+                    // then this task's normalize on what task k-1
+                    // issued.  The last tasks of the last window run
+                    // on into columns nobody uses.
+                    load_task(v0, k + 2, cur);
+                    #pragma unroll
+                    for (int p = 0; p < P; ++p) {
+                        r[p] = rn[p];
+                        rn[p] = corr_mfma<LP>(
+                            nxt[p], sel[((k + 1) >> 1) % SPW][p][0],
+                            (f32x4)0.f);
+                    }
+                } else {
+                    // issue the next task's column loads before this
+                    // task's MFMA + normalize: their latency hides
+                    // under the VALU work
+                    if (k + 1 < NT || w + 1 < w1) load_task(v0, k + 1, nxt);
+                    #pragma unroll
+                    for (int p = 0; p < P; ++p)
+                        r[p] = corr_mfma<LP>(cur[p], sel[si][p][0],
+                                             (f32x4)0.f);
+                }
                 if constexpr (KS == 2) {
                     FragT<LP> c2[P];
                     load_cols(v0, si, st, 1, c2);
@@ -315,7 +374,10 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
                     *(nbf16x4*)dst = zo[p];
                 }
                 #pragma unroll
-                for (int p = 0; p < P; ++p) cur[p] = nxt[p];
+                for (int p = 0; p < P; ++p) {
+                    if constexpr (AHEAD) nxt[p] = cur[p];
+                    else cur[p] = nxt[p];
+                }
             }
         }
         // window image complete.  The other buffer is free: every wave
@@ -394,14 +456,24 @@ extern "C" int fcma_corr_gram_fused_vt(void) { return FS_VT; }
 extern "C" void launch_fcma_corr_gram_fused(
     const void* T1, const void* T2, float* Gout, int LP, ll VA, ll VB,
     ll s0, ll C, int P, int nsplit, int do_shrink, int force_clamp,
-    hipStream_t stream) {
+    int schedule, hipStream_t stream) {
     ll grid = ((C + FS_CB - 1) / FS_CB) * nsplit;
-    #define FS_ONE(TP, TLP)                                              \
-        hipLaunchKernelGGL((k_corr_gram_fused<TP, TLP>), dim3(grid),     \
-                           dim3(64 * FS_NW), 0, stream,                  \
+    // FS_SCHED_AUTO and FS_SCHED_AHEAD take the AHEAD order where the
+    // instance has one, FS_SCHED_PHASED never does
+    const bool ahead = schedule != FS_SCHED_PHASED;
+    #define FS_LAUNCH(TP, TLP, TAHEAD)                                   \
+        hipLaunchKernelGGL((k_corr_gram_fused<TP, TLP, TAHEAD>),         \
+                           dim3(grid), dim3(64 * FS_NW), 0, stream,      \
                            (const bf16_t*)T1,                            \
                            (const bf16_t*)T2, Gout, VA, VB, s0, C,       \
                            nsplit, do_shrink, force_clamp)
+    #define FS_ONE(TP, TLP)                                              \
+        do {                                                             \
+            if constexpr (fs_has_ahead(TLP)) {                           \
+                if (ahead) { FS_LAUNCH(TP, TLP, true); break; }          \
+            }                                                            \
+            FS_LAUNCH(TP, TLP, false);                                   \
+        } while (0)
     if (P == 4) {
         switch (LP) {
             case 16: FS_ONE(4, 16); return;
@@ -416,4 +488,11 @@ extern "C" void launch_fcma_corr_gram_fused(
         }
     }
     #undef FS_ONE
+    #undef FS_LAUNCH
+}
+
+// whether the (P, L) instance has the AHEAD order
+extern "C" int fcma_corr_gram_fused_ahead(int P, ll L) {
+    (void)P;
+    return fs_has_ahead(fused_lp(L));
 }
