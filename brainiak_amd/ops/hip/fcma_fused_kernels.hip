@@ -6,8 +6,13 @@
 // Operands are the time-contiguous cached layout T[64][V][LP] bf16
 // (epoch rows >= E and time steps >= L are zero), LP in {16, 32, 64}.
 // They must be finite: stack_epochs zero-pads and callers z-score with
-// a clamped std.  The clamp test below looks for |r| >= 1 and does not
-// see a NaN.
+// a clamped std.  The clamp test below takes a NaN variance for the
+// mark of a 1 +- r <= 0; a NaN that came in with the operands would send
+// its task through the clamped normalize as well.
+// Columns at or past VB (VB % 16 == 0) are read as zeros: the column
+// loads go through buffer descriptors whose range ends with the epoch
+// row, so a dead 16-column sub-tile has r = 0, z = 0, var = 0 and stores
+// z = 0 by the var <= 0 select, with no test of its own.
 //
 // Work split: a 512-thread workgroup (FS_NW = 8 waves, one per CU)
 // owns FS_CB = 16 selected voxels and sweeps a contiguous range of
@@ -30,10 +35,16 @@
 //           denormal, so the raw v_rsq_f32 equals rsqrtf bit for bit),
 //           bf16; the 4 columns pack into one 8-byte LDS store into
 //           z[c][e][v].  The clamp of the Fisher z (max(1 +- r, 1e-4))
-//           only matters where the bf16 r reaches |r| >= 1, so a task
-//           takes the clamped normalize only when a ballot finds such
-//           an r in the wave; force_clamp takes it for every task.
-//           Both give the same bits.
+//           only matters where the bf16 r reaches |r| >= 1, about one
+//           window of a sweep.  Nobody looks for such an r ahead: every
+//           task runs the unclamped normalize, and always and only
+//           where some 1 +- r <= 0 the log is -inf or NaN, the sum of
+//           squares +inf and var = fma(sq, 1/P, -mean^2) a NaN.  Two
+//           v_cmp_u_f32 per task (the lane's four variances, pairwise)
+//           find that; the wave then normalizes the same correlations
+//           again, clamped, before it stores.  The FORCE instances
+//           (force_clamp) run the clamped normalize for every task and
+//           test nothing.  Both give the same bits.
 //  phase 3  wave w owns voxels 2w, 2w+1: four 16-row bands as bf16x8
 //           fragments, the 10 upper-triangle 16x16x32 MFMAs per voxel;
 //           accumulators (40 fp32 / voxel / lane) persist across the
@@ -87,6 +98,22 @@ __device__ __forceinline__ FragT<LP> load_frag(const bf16_t* row, int q,
     return f;
 }
 
+// the same k-segment through a buffer descriptor: voff is the lane's
+// byte offset from the descriptor's base, bytes at or past num_records
+// read as zero
+template <int LP>
+__device__ __forceinline__ FragT<LP> load_frag_buf(
+    __amdgpu_buffer_rsrc_t rs, unsigned voff) {
+    FragT<LP> f;
+    if constexpr (LP == 16)
+        f.v = __builtin_bit_cast(
+            bf16x4, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0));
+    else
+        f.v = __builtin_bit_cast(
+            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
+    return f;
+}
+
 template <int LP>
 __device__ __forceinline__ f32x4 corr_mfma(const FragT<LP>& a,
                                            const FragT<LP>& b, f32x4 acc) {
@@ -118,12 +145,20 @@ __device__ __forceinline__ f32x4 corr_mfma(const FragT<LP>& a,
 //   sq   = fma(z[P-1], z[P-1], ... fma(z0, z0, z1 * z1))
 //   var  = fma(sq, 1/P, -(mean * mean)),  mean = sum * (1/P)
 //   out  = fma(-sum, 1/P, z) * inv        (= (z - mean) * inv exactly)
+// sum starts from z[0], not 0 + z[0]: z is never -0 (log2(1) is +0 and
+// x - x is +0), so the add changed nothing.
+//
+// Returns the wave's lanes in which the unclamped form met a 1 +- r <= 0
+// (CLAMP = false; always 0 for CLAMP = true).  There, and only there,
+// some z is +-inf or NaN, so sq is +inf or NaN and var is NaN; for
+// |r| < 1 everything is finite.  v_cmp_u_f32 takes two operands, so the
+// four variances of a lane cost two compares, OR-ed on the scalar unit.
 template <int P, bool CLAMP>
-__device__ __forceinline__ void normalize_task(const f32x4 (&rq)[P],
-                                               bool live,
-                                               nbf16x4 (&zo)[P]) {
+__device__ __forceinline__ unsigned long long normalize_task(
+    const f32x4 (&rq)[P], nbf16x4 (&zo)[P]) {
     #pragma clang fp contract(off)
     const f32x2 rP = (f32x2)(1.0f / (float)P);
+    unsigned long long missed = 0;
     #pragma unroll
     for (int h = 0; h < 2; ++h) {
         f32x2 z[P];
@@ -144,7 +179,7 @@ __device__ __forceinline__ void normalize_task(const f32x4 (&rq)[P],
                               __builtin_amdgcn_logf(den[1])};
             z[p] = ln - ld;
         }
-        f32x2 sum = (f32x2)0.f + z[0];
+        f32x2 sum = z[0];
         f32x2 sq = __builtin_elementwise_fma(z[0], z[0], z[1] * z[1]);
         sum += z[1];
         #pragma unroll
@@ -154,12 +189,13 @@ __device__ __forceinline__ void normalize_task(const f32x4 (&rq)[P],
         }
         const f32x2 mean = sum * rP;
         const f32x2 var = __builtin_elementwise_fma(sq, rP, -(mean * mean));
+        if constexpr (!CLAMP)
+            missed |= __builtin_amdgcn_ballot_w64(
+                __builtin_isunordered(var[0], var[1]));
         f32x2 inv;
         #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < 2; ++j)
             inv[j] = (var[j] <= 0.f) ? 0.f : __builtin_amdgcn_rsqf(var[j]);
-            if (!live) inv[j] = 0.f;
-        }
         #pragma unroll
         for (int p = 0; p < P; ++p) {
             const f32x2 o = __builtin_elementwise_fma(-sum, rP, z[p]) * inv;
@@ -167,6 +203,7 @@ __device__ __forceinline__ void normalize_task(const f32x4 (&rq)[P],
             zo[p][2 * h + 1] = (__bf16)o[1];
         }
     }
+    return missed;
 }
 
 // launch_fcma_corr_gram_fused's schedule argument (ext.cpp maps the
@@ -186,11 +223,11 @@ __device__ __forceinline__ void normalize_task(const f32x4 (&rq)[P],
 // bits: the same MFMAs on the same operands.
 static constexpr bool fs_has_ahead(int LP) { return LP <= 32; }
 
-template <int TP, int LP, bool AHEAD>
+template <int TP, int LP, bool AHEAD, bool FORCE>
 __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     const bf16_t* __restrict__ T1, const bf16_t* __restrict__ T2,
     float* __restrict__ Gout, ll VA, ll VB, ll s0, ll C, int nsplit,
-    int do_shrink, int force_clamp) {
+    int do_shrink) {
     constexpr int P = TP;
     constexpr int NSUBJ = FS_E / P;
     constexpr int SPW = NSUBJ / FS_NW;           // subjects per wave
@@ -224,12 +261,8 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
 
     // wave-uniform row base + per-lane 32-bit element offset
     const unsigned sel_off = (unsigned)(csel * LP);
-    const unsigned col_off = (unsigned)(l16 * LP);
     auto sel_row = [&](int e) {
         return T1 + (ll)e * VA * LP + sel_off;
-    };
-    auto col_row = [&](int e, ll v) {
-        return T2 + ((ll)e * VB + v) * LP + col_off;
     };
 
     f32x4 G[FS_VPW][10];
@@ -238,16 +271,72 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
         #pragma unroll
         for (int t = 0; t < 10; ++t) G[i][t] = (f32x4)0.f;
 
-    // task (si, st): subject wv + FS_NW*si, 16-column sub-tile st
+    // task (si, st): subject wv + FS_NW*si, 16-column sub-tile st.
+    // Column fragments come through a buffer descriptor per epoch row and
+    // sub-tile: base = the sub-tile's first column in that row, range =
+    // what is left of the row (nothing at or past VB; VB % 16 == 0, so
+    // whole sub-tiles).  Base and range are scalar (kernel arguments,
+    // blockIdx, the wave index), so the range check sees the lane offset
+    // alone, whatever it does with soffset; the lane keeps one constant
+    // byte offset for the sweep.  A dead sub-tile reads zeros: r = 0,
+    // z = 0, var = 0 and the var <= 0 select stores z = 0.
+    const unsigned col_voff = (unsigned)(l16 * LP * 2)
+        + (LP == 16 ? 8u * q : 16u * q);
     auto load_cols = [&](ll v0, int si, int st, int ks, FragT<LP> dst[P]) {
         const int s = wv + FS_NW * si;
-        // columns past VB (VB % 16 == 0, so whole sub-tiles) read the
-        // last valid rows; their z is forced to 0 below
-        ll v = v0 + st * 16;
-        v = (v < VB) ? v : VB - 16;
+        const ll v = v0 + st * 16;
+        // 32-bit: VB * LP < 2^31 (checked by the caller), and a window
+        // starts less than 64 columns past VB
+        const int left = max((int)VB - (int)v, 0);
+        const unsigned nrec = (unsigned)left * (LP * 2);
+        #pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const bf16_t* base = T2 + ((ll)(s * P + p) * VB + v) * LP;
+            dst[p] = load_frag_buf<LP>(
+                __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, nrec,
+                                                  0x00020000),
+                col_voff + 64u * ks);
+        }
+    };
+
+    // r goes through bf16: same quantisation points as the raw-
+    // correlation tensor of the streamed path.  Two per convert,
+    // unpacked with a shift and a mask.
+    auto quantize = [&](const f32x4 (&r)[P], f32x4 (&rq)[P]) {
         #pragma unroll
         for (int p = 0; p < P; ++p)
-            dst[p] = load_frag<LP>(col_row(s * P + p, v), q, ks);
+            #pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                f32x2 pr = {r[p][2 * h], r[p][2 * h + 1]};
+                unsigned u = __builtin_bit_cast(
+                    unsigned, __builtin_convertvector(pr, nbf16x2));
+                rq[p][2 * h] = __builtin_bit_cast(float, u << 16);
+                rq[p][2 * h + 1] =
+                    __builtin_bit_cast(float, u & 0xffff0000u);
+            }
+    };
+
+    // 8-byte store of a task: columns st*16 + 4q .. +3 of rows (c, e),
+    // e = (wv + FS_NW*si)*P + p, into the image at byte offset img
+    // into the image at byte offset img: row e at e * 64, chunk
+    // st*2 + (q>>1) XORed with (e >> 2) & 3.  That XOR term does not
+    // depend on si or p (FS_NW*si*P is a multiple of 16 and p < P <= 4),
+    // so the swizzled chunk is fixed per lane and sub-tile: one base per
+    // sub-tile, computed once, and the rest of the address is the
+    // immediate offset of the ds_write
+    unsigned char* const zb = &zbuf[0][0];
+    const int swz = ((wv * P) >> 2) & 3;
+    unsigned st_base[2];
+    #pragma unroll
+    for (int st = 0; st < 2; ++st)
+        st_base[st] = l16 * FS_CSTRIDE + wv * P * 64
+            + (((st * 2 + (q >> 1)) ^ swz) << 4) + (q & 1) * 8;
+    auto store_task = [&](unsigned img, int si, int st,
+                          const nbf16x4 (&zo)[P]) {
+        unsigned char* dst = zb + (img + st_base[st]);
+        #pragma unroll
+        for (int p = 0; p < P; ++p)
+            *(nbf16x4*)(dst + (si * FS_NW * P + p) * 64) = zo[p];
     };
 
     // the wave's SPW x P (x KS) selected-voxel fragments do not depend
@@ -264,7 +353,7 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
                     sel_row((wv + FS_NW * si) * P + p), q, ks);
 
     // task k = 2 * si + st of the window at v0; k >= NT runs on into
-    // the next window (past the last column load_cols clamps)
+    // the next window (past the last column the loads return zeros)
     auto load_task = [&](ll v0, int k, FragT<LP> dst[P]) {
         if (k >= NT) { v0 += FS_VT; k -= NT; }
         load_cols(v0, k >> 1, k & 1, 0, dst);
@@ -285,17 +374,52 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
         }
     }
 
+    // What a wave does about a task whose unclamped normalize missed
+    // (FORCE = false).  One-k-step instances redo the task on the spot:
+    // its correlations are still in registers, one branch per task.
+    // The two-k-step instances (LP = 64, 234 .. 255 VGPRs either way)
+    // measured slower that way than the parent and faster this way: they
+    // OR the flags of a window, and a wave with a miss redoes its own
+    // tasks of that window from columns it loads again, in the phased
+    // order, and overwrites its rows of the image in front of the
+    // barrier.  Same MFMAs on the same operands, so the same bits.
+    constexpr bool REDO_WINDOW = KS == 2;
+    auto redo_window = [&](ll v0, unsigned img) {
+        #pragma unroll
+        for (int si = 0; si < SPW; ++si)
+            #pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                f32x4 r[P];
+                #pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    FragT<LP> c[P];
+                    load_cols(v0, si, st, ks, c);
+                    #pragma unroll
+                    for (int p = 0; p < P; ++p)
+                        r[p] = corr_mfma<LP>(c[p], sel[si][p][ks],
+                                             ks ? r[p] : (f32x4)0.f);
+                }
+                f32x4 rq[P];
+                quantize(r, rq);
+                nbf16x4 zo[P];
+                normalize_task<P, true>(rq, zo);
+                store_task(img, si, st, zo);
+            }
+    };
+
     for (ll w = w0; w < w1; ++w) {
         const ll v0 = w * FS_VT;
-        unsigned char* zimg = zbuf[(w - w0) & 1];
+        const unsigned img = (unsigned)((w - w0) & 1) * (FS_CB * FS_CSTRIDE);
+        unsigned char* zimg = zb + img;
+        // lanes whose unclamped normalize met a 1 +- r <= 0, OR-ed over
+        // the tasks of the window
+        unsigned long long missed = 0;
         // fully unrolled (SPW is 2 or 4) so that sel indexes statically
         #pragma unroll
         for (int si = 0; si < SPW; ++si) {
-            const int s = wv + FS_NW * si;
             #pragma unroll
             for (int st = 0; st < 2; ++st) {
                 const int k = 2 * si + st;
-                const bool live = (v0 + st * 16) < VB;   // wave-uniform
                 f32x4 r[P];
                 if constexpr (AHEAD) {
                     // columns of task k+2 out, correlations of task
@@ -329,56 +453,36 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
                         r[p] = corr_mfma<LP>(c2[p], sel[si][p][KS - 1],
                                              r[p]);
                 }
-                // r goes through bf16: same quantisation points as the
-                // raw-correlation tensor of the streamed path.  Two
-                // per convert, unpacked with a shift and a mask.
                 f32x4 rq[P];
-                #pragma unroll
-                for (int p = 0; p < P; ++p)
-                    #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        f32x2 pr = {r[p][2 * h], r[p][2 * h + 1]};
-                        unsigned u = __builtin_bit_cast(
-                            unsigned, __builtin_convertvector(pr, nbf16x2));
-                        rq[p][2 * h] = __builtin_bit_cast(float, u << 16);
-                        rq[p][2 * h + 1] =
-                            __builtin_bit_cast(float, u & 0xffff0000u);
-                    }
-                // clamp on demand: |rq| >= 1 (the diagonal of a self-
-                // correlation, duplicated voxels) is the only case in
-                // which the clamp of the Fisher z changes anything.
-                // One running max per lane, one ballot per task: the
-                // whole wave runs one version.  Dead sub-tiles go
-                // through the same test (their z is forced to 0).
-                float amax = 0.f;
-                #pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    amax = __builtin_fmaxf(__builtin_fmaxf(amax,
-                        __builtin_fabsf(rq[p][0])), __builtin_fabsf(rq[p][1]));
-                    amax = __builtin_fmaxf(__builtin_fmaxf(amax,
-                        __builtin_fabsf(rq[p][2])), __builtin_fabsf(rq[p][3]));
-                }
+                quantize(r, rq);
+                // Clamp found after the fact: |rq| >= 1 (the diagonal of
+                // a self-correlation, duplicated voxels) is the only
+                // case in which the clamp of the Fisher z changes
+                // anything, and exactly there the unclamped normalize
+                // ends in a NaN variance.  Nobody looks for it ahead.
                 nbf16x4 zo[P];
-                if (force_clamp
-                    || __builtin_amdgcn_ballot_w64(!(amax < 1.0f)) != 0)
-                    normalize_task<P, true>(rq, live, zo);
-                else
-                    normalize_task<P, false>(rq, live, zo);
-                // 8-byte store: columns st*16 + 4q .. +3 of row (c, e)
-                const int chunk = st * 2 + (q >> 1);
-                #pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    const int e = s * P + p;
-                    unsigned char* dst = zimg + l16 * FS_CSTRIDE + e * 64
-                        + ((chunk ^ ((e >> 2) & 3)) << 4) + (q & 1) * 8;
-                    *(nbf16x4*)dst = zo[p];
+                if constexpr (FORCE) {
+                    normalize_task<P, true>(rq, zo);
+                } else {
+                    const unsigned long long hit =
+                        normalize_task<P, false>(rq, zo);
+                    if constexpr (REDO_WINDOW) {
+                        missed |= hit;
+                    } else {
+                        if (__builtin_expect(hit != 0, 0))   // wave-uniform
+                            normalize_task<P, true>(rq, zo);
+                    }
                 }
+                store_task(img, si, st, zo);
                 #pragma unroll
                 for (int p = 0; p < P; ++p) {
                     if constexpr (AHEAD) nxt[p] = cur[p];
                     else cur[p] = nxt[p];
                 }
             }
+        }
+        if constexpr (REDO_WINDOW && !FORCE) {
+            if (__builtin_expect(missed != 0, 0)) redo_window(v0, img);
         }
         // window image complete.  The other buffer is free: every wave
         // passed this barrier after its Gram reads of the window before
@@ -461,12 +565,18 @@ extern "C" void launch_fcma_corr_gram_fused(
     // FS_SCHED_AUTO and FS_SCHED_AHEAD take the AHEAD order where the
     // instance has one, FS_SCHED_PHASED never does
     const bool ahead = schedule != FS_SCHED_PHASED;
+    // force_clamp picks the instance that runs the clamped normalize for
+    // every task; the other one finds the tasks that need it afterwards
+    #define FS_LAUNCH_F(TP, TLP, TAHEAD, TFORCE)                         \
+        hipLaunchKernelGGL(                                              \
+            (k_corr_gram_fused<TP, TLP, TAHEAD, TFORCE>),                \
+            dim3(grid), dim3(64 * FS_NW), 0, stream, (const bf16_t*)T1,  \
+            (const bf16_t*)T2, Gout, VA, VB, s0, C, nsplit, do_shrink)
     #define FS_LAUNCH(TP, TLP, TAHEAD)                                   \
-        hipLaunchKernelGGL((k_corr_gram_fused<TP, TLP, TAHEAD>),         \
-                           dim3(grid), dim3(64 * FS_NW), 0, stream,      \
-                           (const bf16_t*)T1,                            \
-                           (const bf16_t*)T2, Gout, VA, VB, s0, C,       \
-                           nsplit, do_shrink, force_clamp)
+        do {                                                             \
+            if (force_clamp) FS_LAUNCH_F(TP, TLP, TAHEAD, true);         \
+            else FS_LAUNCH_F(TP, TLP, TAHEAD, false);                    \
+        } while (0)
     #define FS_ONE(TP, TLP)                                              \
         do {                                                             \
             if constexpr (fs_has_ahead(TLP)) {                           \
@@ -489,6 +599,7 @@ extern "C" void launch_fcma_corr_gram_fused(
     }
     #undef FS_ONE
     #undef FS_LAUNCH
+    #undef FS_LAUNCH_F
 }
 
 // whether the (P, L) instance has the AHEAD order
