@@ -269,6 +269,24 @@ def svm_cv(kernels: torch.Tensor, y: torch.Tensor, train_idx, test_idx,
                          str(variant))
 
 
+def svm_cv_trace(kernels: torch.Tensor, y: torch.Tensor, train_idx,
+                 test_idx, n_train, n_test, C: float = 1.0,
+                 tol: float = 1e-3, max_iter: int = 10000, max_n: int = -1,
+                 variant: str = "auto"):
+    """``svm_cv`` through the trace instantiations of its kernels, for
+    tests: same arguments, returns ``(correct, dec, n_iter)``.
+
+    dec [C, F, E] fp32: the decision value of test sample v of fold f,
+    the number the kernel compares with 0 (slots past n_test[f] are 0).
+    n_iter [C, F] int32: SMO iterations run before the gap fell under
+    tol, or max_iter when it never did.  ``correct`` equals ``svm_cv``'s.
+    """
+    correct, dec, n_iter = _ext().svm_cv_trace(
+        kernels, y, train_idx, test_idx, n_train, n_test, float(C),
+        float(tol), int(max_iter), int(max_n), str(variant))
+    return correct, dec, n_iter
+
+
 def jacobi_eigh(G: torch.Tensor):
     """Batched symmetric eigensolve of G [B, K, K] (K <= 64) → (evals,
     evecs), one wavefront per matrix."""

@@ -46,6 +46,9 @@ void launch_svm_cv(const float*, const float*, const int*, const int*,
                    const int*, const int*, int*, ll, int, int, float,
                    float, int, ll, int, void*);
 int svm_cv_shared_fits(int, ll);
+void launch_svm_cv_trace(const float*, const float*, const int*, const int*,
+                         const int*, const int*, int*, float*, int*, ll,
+                         int, int, float, float, int, ll, int, void*);
 ll fcma_supported_L(ll);
 int fcma_corr_norm_smem(ll, int);
 int fcma_fused_gram_supported(ll, int, ll);
@@ -604,11 +607,13 @@ torch::Tensor tfa_recon(torch::Tensor X, torch::Tensor W, torch::Tensor F,
     return R;
 }
 
-torch::Tensor svm_cv(torch::Tensor kernels, torch::Tensor y,
-                     torch::Tensor train_idx, torch::Tensor test_idx,
-                     torch::Tensor n_train, torch::Tensor n_test,
-                     double Creg, double tol, int64_t max_iter,
-                     int64_t max_n_hint, const std::string& variant) {
+// trace: also return the decision values [C,F,E] and iteration counts
+// [C,F] of the TRACE kernel instantiations (svm_cv_trace, tests only)
+static std::vector<torch::Tensor> svm_cv_impl(
+        torch::Tensor kernels, torch::Tensor y, torch::Tensor train_idx,
+        torch::Tensor test_idx, torch::Tensor n_train, torch::Tensor n_test,
+        double Creg, double tol, int64_t max_iter, int64_t max_n_hint,
+        const std::string& variant, bool trace) {
     check_3d(kernels, torch::kFloat32, "kernels");
     ll C = kernels.size(0);
     int E = (int)kernels.size(1);
@@ -643,13 +648,43 @@ torch::Tensor svm_cv(torch::Tensor kernels, torch::Tensor y,
                          : variant == "wave" ? 2 : 0;
     auto correct = torch::zeros({C, F}, kernels.options()
                                             .dtype(torch::kInt32));
-    launch_svm_cv(kernels.data_ptr<float>(), y.data_ptr<float>(),
-                  train_idx.data_ptr<int>(), test_idx.data_ptr<int>(),
-                  nt.data_ptr<int>(), ns.data_ptr<int>(),
-                  correct.data_ptr<int>(), C, E, F, (float)Creg,
-                  (float)tol, (int)max_iter, max_n, variant_id,
-                  cur_stream());
-    return correct;
+    if (!trace) {
+        launch_svm_cv(kernels.data_ptr<float>(), y.data_ptr<float>(),
+                      train_idx.data_ptr<int>(), test_idx.data_ptr<int>(),
+                      nt.data_ptr<int>(), ns.data_ptr<int>(),
+                      correct.data_ptr<int>(), C, E, F, (float)Creg,
+                      (float)tol, (int)max_iter, max_n, variant_id,
+                      cur_stream());
+        return {correct};
+    }
+    auto dec = torch::zeros({C, F, E}, kernels.options());
+    auto n_iter = torch::zeros({C, F}, correct.options());
+    launch_svm_cv_trace(kernels.data_ptr<float>(), y.data_ptr<float>(),
+                        train_idx.data_ptr<int>(), test_idx.data_ptr<int>(),
+                        nt.data_ptr<int>(), ns.data_ptr<int>(),
+                        correct.data_ptr<int>(), dec.data_ptr<float>(),
+                        n_iter.data_ptr<int>(), C, E, F, (float)Creg,
+                        (float)tol, (int)max_iter, max_n, variant_id,
+                        cur_stream());
+    return {correct, dec, n_iter};
+}
+
+torch::Tensor svm_cv(torch::Tensor kernels, torch::Tensor y,
+                     torch::Tensor train_idx, torch::Tensor test_idx,
+                     torch::Tensor n_train, torch::Tensor n_test,
+                     double Creg, double tol, int64_t max_iter,
+                     int64_t max_n_hint, const std::string& variant) {
+    return svm_cv_impl(kernels, y, train_idx, test_idx, n_train, n_test,
+                       Creg, tol, max_iter, max_n_hint, variant, false)[0];
+}
+
+std::vector<torch::Tensor> svm_cv_trace(
+        torch::Tensor kernels, torch::Tensor y, torch::Tensor train_idx,
+        torch::Tensor test_idx, torch::Tensor n_train, torch::Tensor n_test,
+        double Creg, double tol, int64_t max_iter, int64_t max_n_hint,
+        const std::string& variant) {
+    return svm_cv_impl(kernels, y, train_idx, test_idx, n_train, n_test,
+                       Creg, tol, max_iter, max_n_hint, variant, true);
 }
 
 torch::Tensor stencil3d(torch::Tensor x, torch::Tensor w) {
@@ -974,6 +1009,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "materialized (bf16 MFMA tile pairs)");
     m.def("svm_cv", &svm_cv,
           "batched precomputed-kernel SVC cross-validation",
+          py::arg("kernels"), py::arg("y"), py::arg("train_idx"),
+          py::arg("test_idx"), py::arg("n_train"), py::arg("n_test"),
+          py::arg("C"), py::arg("tol"), py::arg("max_iter"),
+          py::arg("max_n") = -1, py::arg("variant") = "auto");
+    m.def("svm_cv_trace", &svm_cv_trace,
+          "svm_cv through the TRACE kernels: (correct, dec [C,F,E], "
+          "n_iter [C,F]); for tests",
           py::arg("kernels"), py::arg("y"), py::arg("train_idx"),
           py::arg("test_idx"), py::arg("n_train"), py::arg("n_test"),
           py::arg("C"), py::arg("tol"), py::arg("max_iter"),

@@ -8,6 +8,16 @@
 // per lane: VPL=1 covers n_train <= 64, VPL=2 covers n_train <= 128
 // (fp16 tile).
 //
+// The fp16 tile of VPL=2 holds K * 2^-qe, with qe chosen per voxel so that
+// the largest |K| of the voxel's whole [E,E] matrix lands in [2^14, 2^15):
+// the scale is exact, it commutes with the fp16 rounding wherever the
+// unscaled value would have been a normal fp16 number, and it keeps kernels
+// of any fp32 magnitude inside the fp16 range (an unscaled entry above
+// 65504 would be inf, one below 6e-5 subnormal).  The solver therefore
+// trains on the training block rounded to 11 significant bits and predicts
+// with the unrounded fp32 rows.  Both kernels take qe from the same
+// whole-matrix maximum, so their tiles hold the same values.
+//
 // Two kernels, identical counts:
 //  - k_svm_cv: one single-wave workgroup per (voxel, fold), its own
 //    signed Q tile in LDS (variable v = k*64 + lane).  Fallback for
@@ -16,7 +26,9 @@
 //    waves share one staged K tile.  The default wherever it fits.
 //
 // Output: correct-prediction counts [C, F] int32; host divides by test
-// counts and averages folds.
+// counts and averages folds.  The TRACE instantiations (ops.svm_cv_trace,
+// for tests only) also write every test sample's decision value and each
+// QP's iteration count; the production ones carry none of that code.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,7 +36,52 @@
 
 typedef long long ll;
 
+// exponent qe of the fp16 tile scale from m = max |K| of a voxel: m * 2^-qe
+// lies in [2^14, 2^15).  Zero, subnormal and non-finite maxima take qe = 0.
+__device__ __forceinline__ int svm_q_exponent(float m) {
+    const int ex = (__float_as_int(m) >> 23) & 0xff;
+    return (ex == 0 || ex == 255) ? 0 : ex - 127 - 14;
+}
+
 template <int VPL>
+__device__ __forceinline__
+typename std::conditional<VPL == 1, float, _Float16>::type
+svm_q_enc(float x, int qe) {
+    if constexpr (VPL == 1) return x;
+    else return (_Float16)ldexpf(x, -qe);
+}
+
+__device__ __forceinline__ float svm_q_dec(float q, int) { return q; }
+__device__ __forceinline__ float svm_q_dec(_Float16 q, int qe) {
+    return ldexpf((float)q, qe);
+}
+
+__device__ __forceinline__ float wave_absmax(float mx) {
+    #pragma unroll
+    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+    return mx;
+}
+
+// The two-variable instance's step arithmetic, each operation spelled out
+// in the forms k_svm_cv_shared uses (see there), so that the two kernels
+// agree bit for bit whatever the compiler would contract.
+__device__ __forceinline__ float svm_eta2(float Qii, float Qjj, float Qij,
+                                          float yi, float yj) {
+    #pragma clang fp contract(off)
+    return fmaf(-yj, yi * (Qij + Qij), Qii + Qjj);
+}
+
+template <bool FIRST>
+__device__ __forceinline__ float svm_grad2(float g, float qi, float qj,
+                                           float dai, float daj) {
+    #pragma clang fp contract(off)
+    float d;
+    if constexpr (FIRST) d = fmaf(qi, dai, qj * daj);
+    else d = qi * dai + qj * daj;
+    return g + d;
+}
+
+template <int VPL, bool TRACE>
 __global__ __launch_bounds__(64) void k_svm_cv(
     const float* __restrict__ kernels,  // [C, E, E]
     const float* __restrict__ y,        // [E] in {-1, +1}
@@ -33,7 +90,9 @@ __global__ __launch_bounds__(64) void k_svm_cv(
     const int* __restrict__ n_train,    // [F]
     const int* __restrict__ n_test,     // [F]
     int* __restrict__ correct,          // [C, F]
-    ll C, int E, int F, float Creg, float tol, int max_iter) {
+    ll C, int E, int F, float Creg, float tol, int max_iter,
+    float* __restrict__ dec_out,        // [C, F, E], TRACE only
+    int* __restrict__ n_iter_out) {     // [C, F], TRACE only
     constexpr int MAXN = VPL * 64;
     const ll blk = blockIdx.x;
     const ll c = blk / F;
@@ -57,6 +116,16 @@ __global__ __launch_bounds__(64) void k_svm_cv(
     const float* Kc = kernels + c * (ll)E * E;
     const int* tr = train_idx + (ll)f * E;
 
+    // fp16 tile scale from the voxel's whole matrix, as the shared kernel
+    int qe = 0;
+    if constexpr (VPL == 2) {
+        float mx = 0.0f;
+        for (int e = lane; e < E * E; e += 64)
+            mx = fmaxf(mx, fabsf(Kc[e]));
+        qe = __builtin_amdgcn_readfirstlane(
+            svm_q_exponent(wave_absmax(mx)));
+    }
+
     // stage labels + Q = y_i y_j K[tr_i][tr_j]
     float yl[VPL];
     #pragma unroll
@@ -75,7 +144,7 @@ __global__ __launch_bounds__(64) void k_svm_cv(
         if (v < n) {
             const float* krow = Kc + (ll)tr[v] * E;
             for (int j = 0; j < n; ++j)
-                Q[v][j] = (QT)(yl[k] * ys[j] * krow[tr[j]]);
+                Q[v][j] = svm_q_enc<VPL>(yl[k] * ys[j] * krow[tr[j]], qe);
         }
     }
     __syncthreads();
@@ -86,6 +155,7 @@ __global__ __launch_bounds__(64) void k_svm_cv(
     for (int k = 0; k < VPL; ++k) { alpha[k] = 0.0f; grad[k] = -1.0f; }
 
     float b = 0.0f;
+    int iters = max_iter;
     for (int iter = 0; iter < max_iter; ++iter) {
         // per-lane best over its VPL variables, then wave reduce
         float up = -3.0e38f, lo = 3.0e38f;
@@ -113,7 +183,11 @@ __global__ __launch_bounds__(64) void k_svm_cv(
             int li2 = __shfl_xor(lo_i, d);
             if (l2 < lo) { lo = l2; lo_i = li2; }
         }
-        if (up - lo < tol) { b = 0.5f * (up + lo); break; }
+        if (up - lo < tol) {
+            b = 0.5f * (up + lo);
+            if constexpr (TRACE) iters = iter;
+            break;
+        }
         b = 0.5f * (up + lo);
 
         // publish lane-private alpha so lane 0 can read the pair's values
@@ -126,8 +200,12 @@ __global__ __launch_bounds__(64) void k_svm_cv(
         if (lane == 0) {
             int i = up_i, j = lo_i;
             float yi = ys[i], yj = ys[j];
-            float eta = (float)Q[i][i] + (float)Q[j][j]
-                        - 2.0f * (float)Q[i][j] * yi * yj;
+            const float Qii = svm_q_dec(Q[i][i], qe);
+            const float Qjj = svm_q_dec(Q[j][j], qe);
+            const float Qij = svm_q_dec(Q[i][j], qe);
+            float eta;
+            if constexpr (VPL == 2) eta = svm_eta2(Qii, Qjj, Qij, yi, yj);
+            else eta = Qii + Qjj - 2.0f * Qij * yi * yj;
             eta = fmaxf(eta, 1e-12f);
             float t = (up - lo) / eta;
             float ai = alpha_s[i], aj = alpha_s[j];
@@ -147,8 +225,17 @@ __global__ __launch_bounds__(64) void k_svm_cv(
             int v = k * 64 + lane;
             if (v == i) alpha[k] += dai;
             if (v == j) alpha[k] += daj;
-            if (v < n) grad[k] += (float)Q[i][v] * dai
-                                   + (float)Q[j][v] * daj;
+            if (v < n) {
+                const float qi = svm_q_dec(Q[i][v], qe);
+                const float qj = svm_q_dec(Q[j][v], qe);
+                if constexpr (VPL == 2) {
+                    grad[k] = k == 0
+                        ? svm_grad2<true>(grad[k], qi, qj, dai, daj)
+                        : svm_grad2<false>(grad[k], qi, qj, dai, daj);
+                } else {
+                    grad[k] += qi * dai + qj * daj;
+                }
+            }
         }
         __syncthreads();
     }
@@ -172,12 +259,17 @@ __global__ __launch_bounds__(64) void k_svm_cv(
                 dec = fmaf(alpha_s[i], krow[tr[i]], dec);
             float yt = y[te[v]];
             correct_local += ((dec > 0.f) == (yt > 0.f)) ? 1 : 0;
+            if constexpr (TRACE)
+                dec_out[((ll)c * F + f) * E + v] = dec;
         }
     }
     #pragma unroll
     for (int d = 32; d > 0; d >>= 1)
         correct_local += __shfl_xor(correct_local, d);
-    if (lane == 0) correct[c * F + f] = correct_local;
+    if (lane == 0) {
+        correct[c * F + f] = correct_local;
+        if constexpr (TRACE) n_iter_out[c * F + f] = iters;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -208,7 +300,7 @@ __global__ __launch_bounds__(64) void k_svm_cv(
 // trajectory bit for bit: eta = fma(-y_j, y_i*(Q_ij+Q_ij), Q_ii+Q_jj);
 // correctly rounded division; grad + (Q_iv*da_i + Q_jv*da_j) unfused,
 // except the FIRST variable of a two-variable lane, which k_svm_cv<2>
-// contracts to grad + fma(Q_iv, da_i, Q_jv*da_j).
+// computes as grad + fma(Q_iv, da_i, Q_jv*da_j) (svm_grad2 above).
 
 // order-preserving float <-> int32 key (its own inverse): the reduction
 // runs on integers, so the DPP operand folds into v_max_i32/v_min_i32
@@ -249,7 +341,7 @@ __device__ __forceinline__ int first_lane(unsigned long long m) {
     return m ? (int)__ffsll((long long)m) - 1 : 0;
 }
 
-template <int VPL>
+template <int VPL, bool TRACE>
 __global__ __launch_bounds__(512) void k_svm_cv_shared(
     const float* __restrict__ kernels,  // [C, E, E]
     const float* __restrict__ y,        // [E] in {-1, +1}
@@ -258,7 +350,9 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
     const int* __restrict__ n_train,    // [F]
     const int* __restrict__ n_test,     // [F]
     int* __restrict__ correct,          // [C, F]
-    ll C, int E, int F, int S, float Creg, float tol, int max_iter) {
+    ll C, int E, int F, int S, float Creg, float tol, int max_iter,
+    float* __restrict__ dec_out,        // [C, F, E], TRACE only
+    int* __restrict__ n_iter_out) {     // [C, F], TRACE only
     #pragma clang fp contract(off)
     using QT = typename std::conditional<VPL == 1, float, _Float16>::type;
     extern __shared__ char smem_raw[];
@@ -269,6 +363,21 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
     const float* Kc = kernels + c * (ll)E * E;
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int EE = E * E;
+
+    // fp16 tile scale from the voxel's whole matrix, as k_svm_cv<2>
+    int qe = 0;
+    if constexpr (VPL == 2) {
+        __shared__ float wmax[8];
+        float mx = 0.0f;
+        for (int e = tid; e < EE; e += nthr)
+            mx = fmaxf(mx, fabsf(Kc[e]));
+        mx = wave_absmax(mx);
+        if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+        __syncthreads();
+        mx = wmax[0];
+        for (int w = 1; w < (nthr >> 6); ++w) mx = fmaxf(mx, wmax[w]);
+        qe = __builtin_amdgcn_readfirstlane(svm_q_exponent(mx));
+    }
 
     // stage K once for all folds: 16-byte coalesced loads when the
     // voxel's matrix is 16-byte aligned (E even and an aligned base)
@@ -282,7 +391,7 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
             int cc = q * 4 - r * E;
             #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                tile[r * S + cc] = (QT)vv[u];
+                tile[r * S + cc] = svm_q_enc<VPL>(vv[u], qe);
                 if (++cc == E) { cc = 0; ++r; }
             }
         }
@@ -290,7 +399,7 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
     }
     for (int e = done + tid; e < EE; e += nthr) {
         int r = e / E;
-        tile[r * S + (e - r * E)] = (QT)Kc[e];
+        tile[r * S + (e - r * E)] = svm_q_enc<VPL>(Kc[e], qe);
     }
     __syncthreads();
     // ---- no block-level barrier from here on ----
@@ -317,12 +426,14 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
             valid[k] = v < n;
             col[k] = valid[k] ? tr[v] : 0;
             yl[k] = valid[k] ? y[col[k]] : 0.0f;
-            qd[k] = (float)tile[col[k] * S + col[k]];   // Q_vv = K_vv
+            // Q_vv = K_vv
+            qd[k] = svm_q_dec(tile[col[k] * S + col[k]], qe);
             alpha[k] = 0.0f;
             grad[k] = -1.0f;
         }
 
         float b = 0.0f;
+        int iters = max_iter;
         for (int iter = 0; iter < max_iter; ++iter) {
             // per-lane best over its VPL variables (k=0 wins ties)
             float uv = -3.0e38f, lv = 3.0e38f;
@@ -350,7 +461,10 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
             const float lo = lane_f(lv, lj);
             const float gap = __fsub_rn(up, lo);
             b = __fmul_rn(0.5f, __fadd_rn(up, lo));
-            if (gap < tol) break;
+            if (gap < tol) {
+                if constexpr (TRACE) iters = iter;
+                break;
+            }
 
             // each lane's own candidate, then the pair's via readlane
             float yu = yl[0], au = alpha[0], du = qd[0];
@@ -374,8 +488,8 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
             float qi[VPL], qj[VPL];
             #pragma unroll
             for (int k = 0; k < VPL; ++k) {
-                float a = (float)tile[ri + col[k]];
-                float bq = (float)tile[rj + col[k]];
+                float a = svm_q_dec(tile[ri + col[k]], qe);
+                float bq = svm_q_dec(tile[rj + col[k]], qe);
                 qi[k] = __fmul_rn(__fmul_rn(yi, yl[k]), a);
                 qj[k] = __fmul_rn(__fmul_rn(yj, yl[k]), bq);
             }
@@ -442,8 +556,13 @@ __global__ __launch_bounds__(512) void k_svm_cv_shared(
             }
             correct_w += __popcll(__ballot(
                 act && ((dec > 0.f) == (yt > 0.f))));
+            if constexpr (TRACE)
+                if (act) dec_out[(c * F + f) * E + tv] = dec;
         }
-        if (lane == 0) correct[c * F + f] = correct_w;
+        if (lane == 0) {
+            correct[c * F + f] = correct_w;
+            if constexpr (TRACE) n_iter_out[c * F + f] = iters;
+        }
     }
 }
 
@@ -463,39 +582,69 @@ extern "C" int svm_cv_shared_fits(int E, ll max_n) {
 }
 
 // variant: 0 = auto (shared when it fits), 1 = shared, 2 = one wave per QP
+template <bool TRACE>
+static void launch_svm_cv_t(const float* kernels, const float* y,
+                            const int* train_idx, const int* test_idx,
+                            const int* n_train, const int* n_test,
+                            int* correct, float* dec, int* n_iter, ll C,
+                            int E, int F, float Creg, float tol,
+                            int max_iter, ll max_n, int variant,
+                            hipStream_t stream) {
+    const size_t shared_smem = svm_cv_shared_smem(E, max_n);
+    if (variant != 2 && shared_smem != 0) {
+        const int W = F < 8 ? F : 8;
+        const int S = E | 1;
+        if (max_n <= 64)
+            hipLaunchKernelGGL((k_svm_cv_shared<1, TRACE>),
+                               dim3((unsigned)C), dim3(64 * W), shared_smem,
+                               stream, kernels, y, train_idx, test_idx,
+                               n_train, n_test, correct, C, E, F, S, Creg,
+                               tol, max_iter, dec, n_iter);
+        else
+            hipLaunchKernelGGL((k_svm_cv_shared<2, TRACE>),
+                               dim3((unsigned)C), dim3(64 * W), shared_smem,
+                               stream, kernels, y, train_idx, test_idx,
+                               n_train, n_test, correct, C, E, F, S, Creg,
+                               tol, max_iter, dec, n_iter);
+        return;
+    }
+    if (max_n <= 64) {
+        size_t smem = (size_t)64 * 65 * 4 + 2 * 64 * 4;
+        hipLaunchKernelGGL((k_svm_cv<1, TRACE>), dim3((unsigned)(C * F)),
+                           dim3(64), smem, stream, kernels, y, train_idx,
+                           test_idx, n_train, n_test, correct, C, E, F,
+                           Creg, tol, max_iter, dec, n_iter);
+        return;
+    }
+    size_t smem = (size_t)128 * 129 * 2 + 2 * 128 * 4;   // fp16 Q
+    hipLaunchKernelGGL((k_svm_cv<2, TRACE>), dim3((unsigned)(C * F)),
+                       dim3(64), smem, stream, kernels, y, train_idx,
+                       test_idx, n_train, n_test, correct, C, E, F, Creg,
+                       tol, max_iter, dec, n_iter);
+}
+
 extern "C" void launch_svm_cv(const float* kernels, const float* y,
                               const int* train_idx, const int* test_idx,
                               const int* n_train, const int* n_test,
                               int* correct, ll C, int E, int F, float Creg,
                               float tol, int max_iter, ll max_n,
                               int variant, hipStream_t stream) {
-    const size_t shared_smem = svm_cv_shared_smem(E, max_n);
-    if (variant != 2 && shared_smem != 0) {
-        const int W = F < 8 ? F : 8;
-        const int S = E | 1;
-        if (max_n <= 64)
-            hipLaunchKernelGGL(k_svm_cv_shared<1>, dim3((unsigned)C),
-                               dim3(64 * W), shared_smem, stream, kernels,
-                               y, train_idx, test_idx, n_train, n_test,
-                               correct, C, E, F, S, Creg, tol, max_iter);
-        else
-            hipLaunchKernelGGL(k_svm_cv_shared<2>, dim3((unsigned)C),
-                               dim3(64 * W), shared_smem, stream, kernels,
-                               y, train_idx, test_idx, n_train, n_test,
-                               correct, C, E, F, S, Creg, tol, max_iter);
-        return;
-    }
-    if (max_n <= 64) {
-        size_t smem = (size_t)64 * 65 * 4 + 2 * 64 * 4;
-        hipLaunchKernelGGL(k_svm_cv<1>, dim3((unsigned)(C * F)), dim3(64),
-                           smem, stream, kernels, y, train_idx, test_idx,
-                           n_train, n_test, correct, C, E, F, Creg, tol,
-                           max_iter);
-        return;
-    }
-    size_t smem = (size_t)128 * 129 * 2 + 2 * 128 * 4;   // fp16 Q
-    hipLaunchKernelGGL(k_svm_cv<2>, dim3((unsigned)(C * F)), dim3(64),
-                       smem, stream, kernels, y, train_idx, test_idx,
-                       n_train, n_test, correct, C, E, F, Creg, tol,
-                       max_iter);
+    launch_svm_cv_t<false>(kernels, y, train_idx, test_idx, n_train, n_test,
+                           correct, nullptr, nullptr, C, E, F, Creg, tol,
+                           max_iter, max_n, variant, stream);
+}
+
+// the same launch through the TRACE instantiations: dec [C, F, E] fp32 and
+// n_iter [C, F] int32 are written next to the counts (tests only)
+extern "C" void launch_svm_cv_trace(const float* kernels, const float* y,
+                                    const int* train_idx,
+                                    const int* test_idx, const int* n_train,
+                                    const int* n_test, int* correct,
+                                    float* dec, int* n_iter, ll C, int E,
+                                    int F, float Creg, float tol,
+                                    int max_iter, ll max_n, int variant,
+                                    hipStream_t stream) {
+    launch_svm_cv_t<true>(kernels, y, train_idx, test_idx, n_train, n_test,
+                          correct, dec, n_iter, C, E, F, Creg, tol,
+                          max_iter, max_n, variant, stream);
 }

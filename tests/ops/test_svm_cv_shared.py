@@ -9,8 +9,10 @@ only its fixed point.  A different tie-break among equal scores or a
 differently rounded update changes the pair picked within the first few
 iterations and with it the truncated runs' predictions.
 
-The wave kernel itself is held to sklearn by
-``test_hip_ops.py::test_svm_cv_kernel_matches_sklearn``.
+What the two kernels share (bias rule, box slack, eta clamp, fp16 tile,
+prediction chain, ``max_iter`` exit) is invisible here; both are held to
+an fp64 sklearn optimum, decision value by decision value, by
+``test_svm_cv_oracle.py``.
 """
 
 import numpy as np
