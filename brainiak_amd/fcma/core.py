@@ -241,22 +241,6 @@ class CorrelationPipeline:
         E = self.num_epochs
         Epad = ((E + 63) // 64) * 64
         ext = ops.load_extension()
-        if getattr(ext, "fcma_fused_gram_native", None) is not None and \
-                ext.fcma_fused_gram_native(E, self.epochs_per_subj,
-                                           self.data.shape[1]) and \
-                os.environ.get("BRAINIAK_FUSED"):
-            # single-kernel corr+gram (opt-in): Z never touches HBM, but
-            # measured on MI355X the B-read amplification at its 8-voxel
-            # c-tile outweighs the saved Z round trip (24.7 vs 16.7
-            # ms/step, profiles/README.md) — the streamed two-kernel
-            # pipeline below with a 64-voxel corr tile wins
-            gram = torch.cat([
-                ops.fcma_fused_gram(self.data, self.data2, s, c,
-                                    self.epochs_per_subj)
-                for s, c in chunks], dim=0)
-            if shrink:
-                _shrink_(gram)
-            return gram
         max_count = max(c for _, c in chunks)
         # persistent double-buffered Z workspace: repeated multi-GB
         # allocations churn the caching allocator across streams
@@ -275,25 +259,18 @@ class CorrelationPipeline:
             # the two kernels (the scheduler starves the gram stream
             # while any corr block is pending — measured exactly
             # corr+gram serial); equal priority lets them co-schedule
-            # (BRAINIAK_CORR_PRIO=-1 re-enables the experiment)
-            prio = int(os.environ.get("BRAINIAK_CORR_PRIO", "0"))
             self._streams = (
-                torch.cuda.Stream(device=self.device, priority=prio),
+                torch.cuda.Stream(device=self.device),
                 torch.cuda.Stream(device=self.device))
         corr_stream, gram_stream = self._streams
         grams = []
         pending = None          # (z, ready-event, buffer index)
         buf_free = [None, None]  # event: gram done reading buffer b
 
-        skip_gram = bool(os.environ.get("BRAINIAK_SKIP_GRAM"))  # probe
-
         def _consume(z, ev, bidx):
             with torch.cuda.stream(gram_stream):
                 gram_stream.wait_event(ev)
-                if skip_gram:
-                    g = torch.zeros((z.shape[0], Epad, Epad),
-                                    dtype=torch.float32, device=z.device)
-                elif self.z_fp8:
+                if self.z_fp8:
                     g = ops.fcma_gram_fp8(z)
                 else:
                     g = ops.fcma_gram_bf16(

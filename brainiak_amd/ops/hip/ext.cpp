@@ -12,31 +12,12 @@
 #include <climits>
 #include <string>
 
+#include "fcma_launch.h"   // everything fcma_kernels.hip exports
+
 typedef long long ll;
 
+// the other kernel files' launchers (void* stands in for hipStream_t)
 extern "C" {
-void launch_fcma_normalize(float*, ll, ll, ll, int, void*);
-void launch_fcma_corr_norm(const void*, const void*, void*, float*, ll, ll,
-                           ll, ll, ll, ll, int, int, ll, void*,
-                           const void*);
-int fcma_corr_variant(void);
-int fcma_corr_norm_smem(ll, int);
-void launch_fcma_gram_bf16(const void*, float*, ll, ll, ll, ll, void*);
-void launch_fcma_gram_fp8(const void*, float*, ll, ll, ll, ll, void*);
-void launch_fcma_gram_f32(const float*, float*, ll, ll, ll, void*);
-int fcma_corr_norm_z8_supported(ll, int, ll);
-void launch_fp8_cvt_probe(const float*, void*, ll, void*);
-void launch_fcma_corr_raw(const void*, const void*, void*, ll, ll, ll,
-                          ll, ll, int, void*);
-void launch_fcma_gram_bf16_norm(const void*, float*, ll, ll, ll, ll,
-                                int, void*);
-void launch_fcma_corr_gram_duo(const void*, const void*, void*, ll, ll,
-                               ll, ll, ll, int, const void*, float*,
-                               ll, ll, ll, ll, const float*, float*,
-                               ll, ll, int, void*);
-void launch_fp8_cvt_probe_sw(const float*, void*, ll, void*);
-void launch_fcma_corr_norm_z8(const void*, const void*, void*, ll, ll,
-                              ll, ll, ll, int, void*);
 void launch_jacobi_eigh(const float*, float*, float*, ll, int, void*);
 void launch_tfa_factor(const float*, const float*, const float*, float*,
                        ll, int, void*);
@@ -49,16 +30,11 @@ int svm_cv_shared_fits(int, ll);
 void launch_svm_cv_trace(const float*, const float*, const int*, const int*,
                          const int*, const int*, int*, float*, int*, ll,
                          int, int, float, float, int, ll, int, void*);
-ll fcma_supported_L(ll);
-int fcma_corr_norm_smem(ll, int);
-int fcma_fused_gram_supported(ll, int, ll);
 void launch_isfc_accum(float*, const void*, ll, ll, int, void*);
 void launch_isfc_fused(float*, const void*, const void*, ll, ll, ll,
                        void*);
 void launch_stencil3d(const float*, const float*, float*, ll, int, int,
                       int, int, void*);
-void launch_fcma_fused_corr_gram(const void*, const void*, float*, ll,
-                                 ll, ll, ll, ll, int, void*);
 int fcma_corr_gram_fused_supported(ll, int, ll);
 int fcma_corr_gram_fused_lp(ll);
 int fcma_corr_gram_fused_cb(void);
@@ -67,7 +43,6 @@ int fcma_corr_gram_fused_ahead(int, ll);
 void launch_fcma_corr_gram_fused(const void*, const void*, float*, int, ll,
                                  ll, ll, ll, int, int, int, int, int,
                                  void*);
-void launch_fcma_gsum(const float*, float*, ll, ll, ll, int, void*);
 void launch_hmm_fb(const double*, const double*, const double*,
                    const double*, const double*, const int*, const int*,
                    double*, double*, ll, int, int, void*);
@@ -90,8 +65,8 @@ void launch_sl_gram(const float*, const unsigned char*,
 int sl_gram_max_e(void);
 }
 
-static void* cur_stream() {
-    return (void*)at::cuda::getCurrentCUDAStream().stream();
+static hipStream_t cur_stream() {
+    return at::cuda::getCurrentCUDAStream().stream();
 }
 
 static void check_3d(const torch::Tensor& t, c10::ScalarType dt,
@@ -113,6 +88,12 @@ torch::Tensor fcma_normalize_(torch::Tensor corr, int64_t P) {
     return corr;
 }
 
+static const char* const kBadL =
+    "epoch length must be padded to one of {8,12,16,20,24,28,32,36,40}";
+// a (P, L)-templated launcher found no instantiation and launched nothing
+static const char* const kNoKernel =
+    "no FCMA kernel instantiation for this shape: ";
+
 static int pick_p_for_raw(ll E) {
     for (int p : {8, 4, 2}) if (E % p == 0) return p;
     return 1;
@@ -125,15 +106,15 @@ torch::Tensor fcma_correlate(torch::Tensor A, torch::Tensor B,
     ll E = A.size(0), L = A.size(1), VA = A.size(2), VB = B.size(2);
     TORCH_CHECK(B.size(0) == E && B.size(1) == L, "A/B epoch shapes differ");
     TORCH_CHECK(start >= 0 && start + count <= VA, "voxel range");
-    TORCH_CHECK(fcma_supported_L(L) == L,
-                "epoch length must be padded to one of {8,16,24,32,40}");
+    TORCH_CHECK(fcma_supported_L(L) == L, kBadL);
     int P = pick_p_for_raw(E);
     auto out = torch::empty({count, E, VB},
                             A.options().dtype(torch::kFloat32));
-    launch_fcma_corr_norm(A.data_ptr(), B.data_ptr(), nullptr,
-                          out.data_ptr<float>(), E, L, VA, VB, start,
-                          count, P, /*mode=*/2, E, cur_stream(),
-                          nullptr);
+    TORCH_CHECK(launch_fcma_corr_norm(A.data_ptr(), B.data_ptr(), nullptr,
+                                      out.data_ptr<float>(), E, L, VA, VB,
+                                      start, count, P, /*mode=*/2, E,
+                                      cur_stream(), nullptr),
+                kNoKernel, "P=", P, " L=", L);
     return out;
 }
 
@@ -151,8 +132,7 @@ torch::Tensor fcma_corr_norm_z(torch::Tensor A, torch::Tensor B,
     TORCH_CHECK(P <= 32, "epochs_per_subj > 32: use the staged path");
     TORCH_CHECK(fcma_corr_norm_smem(L, (int)P) <= 160 * 1024,
                 "corr tile exceeds gfx950 LDS; use the staged path");
-    TORCH_CHECK(fcma_supported_L(L) == L,
-                "epoch length must be padded to one of {8,16,24,32,40}");
+    TORCH_CHECK(fcma_supported_L(L) == L, kBadL);
     ll Eout = std::max((ll)padE, E);
     torch::Tensor Z;
     bool fp8 = false;
@@ -173,11 +153,12 @@ torch::Tensor fcma_corr_norm_z(torch::Tensor A, torch::Tensor B,
         Z = (Eout == E) ? torch::empty({count, E, VB}, A.options())
                         : torch::zeros({count, Eout, VB}, A.options());
     }
-    // dot3s variant reads the A operand voxel-major through the
+    // the dot3s kernel (P in {2,4}: every raw and fp8 launch, and the
+    // bf16 corr+norm one) reads the A operand voxel-major through the
     // scalar path: hand it the [count, E, L] transposed slice
     torch::Tensor At;
     const void* At_ptr = nullptr;
-    if (fcma_corr_variant() >= 3) {
+    if (P == 2 || P == 4) {
         At = A.narrow(2, start, count).permute({2, 0, 1}).contiguous();
         At_ptr = At.data_ptr();
     }
@@ -185,27 +166,28 @@ torch::Tensor fcma_corr_norm_z(torch::Tensor A, torch::Tensor B,
     if (raw) {
         TORCH_CHECK(!fp8, "raw correlations are bf16-only (e4m3 cannot "
                           "resolve r near +-1 before Fisher-z)");
-        TORCH_CHECK(At_ptr != nullptr && (P == 2 || P == 4),
-                    "raw mode needs the dot3s variant and P in {2,4}");
-        launch_fcma_corr_raw(At_ptr, B.data_ptr(), Z.data_ptr(),
-                             E, L, VB, count, Eout, (int)P,
-                             cur_stream());
+        TORCH_CHECK(At_ptr != nullptr, "raw mode needs P in {2,4}");
+        TORCH_CHECK(launch_fcma_corr_raw(At_ptr, B.data_ptr(),
+                                         Z.data_ptr(), E, L, VB, count,
+                                         Eout, (int)P, cur_stream()),
+                    kNoKernel, "raw P=", P, " L=", L);
         return Z;
     }
     if (fp8) {
-        TORCH_CHECK(At_ptr != nullptr,
-                    "fp8 Z output needs the dot3s corr kernel "
-                    "(BRAINIAK_CORR_KERNEL=dot3s, the default)");
         TORCH_CHECK(fcma_corr_norm_z8_supported(E, (int)P, L),
                     "fp8 Z output needs P in {2,4} and even L");
-        launch_fcma_corr_norm_z8(At_ptr, B.data_ptr(), Z.data_ptr(),
-                                 E, L, VB, count, Eout, (int)P,
-                                 cur_stream());
+        TORCH_CHECK(launch_fcma_corr_norm_z8(At_ptr, B.data_ptr(),
+                                             Z.data_ptr(), E, L, VB,
+                                             count, Eout, (int)P,
+                                             cur_stream()),
+                    kNoKernel, "fp8 P=", P, " L=", L);
         return Z;
     }
-    launch_fcma_corr_norm(A.data_ptr(), B.data_ptr(), Z.data_ptr(),
-                          nullptr, E, L, VA, VB, start, count, (int)P,
-                          /*mode=*/0, Eout, cur_stream(), At_ptr);
+    TORCH_CHECK(launch_fcma_corr_norm(A.data_ptr(), B.data_ptr(),
+                                      Z.data_ptr(), nullptr, E, L, VA, VB,
+                                      start, count, (int)P, /*mode=*/0,
+                                      Eout, cur_stream(), At_ptr),
+                kNoKernel, "P=", P, " L=", L);
     return Z;
 }
 
@@ -316,11 +298,12 @@ void fcma_corr_gram_duo(torch::Tensor A, torch::Tensor B,
         gps_ptr = Gp.data_ptr<float>();
         gso_ptr = Go.data_ptr<float>();
     }
-    launch_fcma_corr_gram_duo(At.data_ptr(), B.data_ptr(),
-                              Zout.data_ptr(), E, L, VB, count, Eout,
-                              (int)P, zprev_ptr, g_ptr, Cg, Eg, Vg,
-                              nsplit, gps_ptr, gso_ptr, Cs, nsplit_sum,
-                              shrink ? 1 : 0, cur_stream());
+    TORCH_CHECK(launch_fcma_corr_gram_duo(
+                    At.data_ptr(), B.data_ptr(), Zout.data_ptr(), E, L,
+                    VB, count, Eout, (int)P, zprev_ptr, g_ptr, Cg, Eg,
+                    Vg, nsplit, gps_ptr, gso_ptr, Cs, nsplit_sum,
+                    shrink ? 1 : 0, cur_stream()),
+                kNoKernel, "duo P=", P, " L=", L);
 }
 
 torch::Tensor debug_fp8_cvt(torch::Tensor x, bool sw) {
@@ -399,9 +382,10 @@ torch::Tensor fcma_fused_gram(torch::Tensor A, torch::Tensor B,
             vTiles, std::max((ll)1, (511 + cTiles) / cTiles));
         auto G = torch::empty({nsplit, count, E, E},
                               A.options().dtype(torch::kFloat32));
-        launch_fcma_fused_corr_gram(A.data_ptr(), B.data_ptr(),
-                                    G.data_ptr<float>(), L, VA, VB,
-                                    start, count, nsplit, cur_stream());
+        TORCH_CHECK(launch_fcma_fused_corr_gram(
+                        A.data_ptr(), B.data_ptr(), G.data_ptr<float>(),
+                        L, VA, VB, start, count, nsplit, cur_stream()),
+                    kNoKernel, "fused L=", L);
         return nsplit == 1 ? G.squeeze(0) : G.sum(0);
     }
     ll Epad = ((E + 63) / 64) * 64;

@@ -7,12 +7,13 @@
 //
 // Design (per /opt/skills/guides/cdna_hip_programming.md):
 //  * wave64, 256-thread blocks.
-//  * The correlation+normalization stage ships FOUR measured variants
-//    (profiles/README.md has the ladder): classic (pk_fma),
-//    dot2 (v_dot2c_f32_bf16 + fused normalize/store), dot3
-//    (thread-owns-all-epochs, no corr LDS tile), and the default dot3s
-//    (dot3 with the wave-uniform A operand on the SCALAR path — no LDS,
-//    no barriers).  BRAINIAK_CORR_KERNEL selects a variant at runtime.
+//  * The correlation+normalization stage ships the two variants that won
+//    their measurements (profiles/README.md has the ladder and the
+//    losers' numbers): dot3s (thread owns all P epochs of a column, the
+//    wave-uniform A operand on the SCALAR path — no LDS, no barriers)
+//    for bf16 Z with P in {2,4}, and dot2 (v_dot2c_f32_bf16 + fused
+//    normalize/store) for everything else.  launch_corr_norm_t holds
+//    that rule; dispatch_pl maps a runtime (P, L) onto the templates.
 //  * k_gram_bf16: G_c = Z_c Z_c^T via v_mfma_f32_16x16x32_bf16, T14
 //    issue-early K-tiles, V-split partials so small-C calls fill the
 //    256 CUs.  k_fused_corr_gram: the whole chunk in one kernel
@@ -24,10 +25,13 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
-#include <stdlib.h>
-#include <string.h>
+
+#include <iterator>
+#include <type_traits>
+#include <utility>
 
 #include "fcma_common.h"
+#include "fcma_launch.h"
 
 // --- fp8 (OCP e4m3fn) Z-tile path -----------------------------------------
 // The normalized Z values are within-subject z-scores, bounded by
@@ -116,166 +120,27 @@ __global__ __launch_bounds__(256) void k_normalize(
 }
 
 // ===========================================================================
-// k_corr_norm: fused correlation + normalization for one
-// (voxel-tile CT=16, subject, column-tile VT=64):
+// The corr kernels: fused correlation + normalization for one
+// (voxel-tile, subject, column-tile):
 //   corr[c,p,v] = sum_k A[s*P+p, k, s0+c0+c] * B[s*P+p, k, v0+v]
 //   out        = zscore_p(fisher_z(corr))        (modes 0/1)
 // A: [E, L, VA] bf16, B: [E, L, VB] bf16 (stacked z-scored epochs; zero
-// padding rows are inert).  mode 0: bf16 Z out; 1: fp32 normalized out;
-// 2: fp32 RAW correlation out (no normalization).
-// B-tile elements are reused across the CT voxels from per-thread
-// registers - LLC traffic scales as 1/CT.
+// padding rows are inert).  mode 0: bf16 Z out; 2: fp32 RAW correlation
+// out (no normalization).  The launchers pass nothing else: the kernels'
+// mode 1 (fp32 normalized out) and mode 3 (write-skip probe) branches
+// are dead and stay only so that the generated code does not move.
+// TL = compile-time epoch length (the host pads epochs to a supported
+// length with zero rows) so the per-thread B column stays in registers
+// with fully unrolled dot chains.
 // ===========================================================================
 #define CN_CT 16
 #define CN_VT 64
-#define CN_MAXL 40
-
-// TL = compile-time epoch length (host pads epochs to {8,16,24,32,40}
-// with zero rows, which are inert for z-scored data) so the per-thread
-// B column stays in registers with fully unrolled FMA chains.
-template <int TP, int TL>
-__global__ __launch_bounds__(256) void k_corr_norm(
-    const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
-    bf16_t* __restrict__ zOut, float* __restrict__ fOut,
-    ll E, ll Lrt, ll VA, ll VB, ll s0, ll C, int Prt, int mode,
-    ll zstride) {
-    const int P = TP > 0 ? TP : Prt;
-    const ll L = TL;
-    (void)Lrt;
-    const ll nSubj = E / P;
-    const ll cTiles = (C + CN_CT - 1) / CN_CT;
-    const ll vTiles = (VB + CN_VT - 1) / CN_VT;
-    ll b = blockIdx.x;
-    const ll vt = b % vTiles; b /= vTiles;
-    const ll s = b % nSubj;   b /= nSubj;
-    const ll ct = b;
-    if (ct >= cTiles) return;
-
-    const ll c0 = ct * CN_CT;
-    const ll v0 = vt * CN_VT;
-    const int CT = (int)min((ll)CN_CT, C - c0);
-    const int VT = (int)min((ll)CN_VT, VB - v0);
-    const int tid = threadIdx.x;
-
-    extern __shared__ char smem[];
-    float* a_tile = (float*)smem;                      // [P][L][CN_CT] f32
-    float* corr = a_tile + (size_t)P * L * CN_CT;
-    // corr: [CN_CT][P][CN_VT]
-
-    // stage A columns converted to fp32 ONCE (per-FMA bf16 converts in
-    // the hot loop were ~1/3 of the kernel's VALU work)
-    for (int idx = tid; idx < P * (int)L * CN_CT; idx += 256) {
-        int c = idx % CN_CT;
-        int k = (idx / CN_CT) % (int)L;
-        int p = idx / (CN_CT * (int)L);
-        float val = 0.0f;
-        if (c < CT)
-            val = (float)A[((s * P + p) * L + k) * VA + (s0 + c0 + c)];
-        a_tile[idx] = val;
-    }
-    __syncthreads();
-
-    for (int base = tid; base < P * CN_VT; base += 256) {
-        int v = base % CN_VT;
-        int p = base / CN_VT;
-        if (v < VT) {
-            float breg[TL];
-            const bf16_t* brow = B + ((s * P + p) * L) * VB + (v0 + v);
-            #pragma unroll
-            for (int k = 0; k < TL; ++k)
-                breg[k] = (float)brow[(ll)k * VB];
-            // k-outer / c-inner with a 16-wide register accumulator:
-            // 4x f32x4 LDS broadcast reads + 16 FMA per k-step
-            f32x4 acc[CN_CT / 4];
-            #pragma unroll
-            for (int q = 0; q < CN_CT / 4; ++q) acc[q] = (f32x4)0.f;
-            const f32x4* arow4 =
-                (const f32x4*)(a_tile + ((size_t)p * L) * CN_CT);
-            #pragma unroll
-            for (int k = 0; k < TL; ++k) {
-                float bk = breg[k];
-                #pragma unroll
-                for (int q = 0; q < CN_CT / 4; ++q) {
-                    f32x4 a4 = arow4[k * (CN_CT / 4) + q];
-                    acc[q] += a4 * bk;
-                }
-            }
-            #pragma unroll
-            for (int q = 0; q < CN_CT / 4; ++q)
-                #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    corr[((size_t)(4 * q + j) * P + p) * CN_VT + v] =
-                        acc[q][j];
-        }
-    }
-    __syncthreads();
-
-    if (mode == 2) {
-        for (int base = tid; base < CT * P * CN_VT; base += 256) {
-            int v = base % CN_VT;
-            int p = (base / CN_VT) % P;
-            int c = base / (CN_VT * P);
-            if (v < VT)
-                fOut[((c0 + c) * E + (s * P + p)) * VB + v0 + v] =
-                    corr[((size_t)c * P + p) * CN_VT + v];
-        }
-        return;
-    }
-
-    // normalization: one thread per (c, v) column over the P epochs
-    for (int base = tid; base < CT * CN_VT; base += 256) {
-        int v = base % CN_VT;
-        int c = base / CN_VT;
-        if (v >= VT) continue;
-        float* col = corr + ((size_t)c * P) * CN_VT + v;
-        float mean = 0.f, sq = 0.f;
-        if (TP > 0) {
-            float z[TP > 0 ? TP : 1];
-            #pragma unroll
-            for (int p = 0; p < P; ++p) {
-                z[p] = fisher_z(col[(size_t)p * CN_VT]);
-                mean += z[p]; sq += z[p] * z[p];
-            }
-            mean /= (float)P;
-            float var = sq / (float)P - mean * mean;
-            float inv = (var <= 0.f) ? 0.f : rsqrtf(var);
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                col[(size_t)p * CN_VT] = (z[p] - mean) * inv;
-        } else {
-            for (int p = 0; p < P; ++p) {
-                float zv = fisher_z(col[(size_t)p * CN_VT]);
-                mean += zv; sq += zv * zv;
-                col[(size_t)p * CN_VT] = zv;   // store transformed
-            }
-            mean /= (float)P;
-            float var = sq / (float)P - mean * mean;
-            float inv = (var <= 0.f) ? 0.f : rsqrtf(var);
-            for (int p = 0; p < P; ++p)
-                col[(size_t)p * CN_VT] = (col[(size_t)p * CN_VT] - mean)
-                                         * inv;
-        }
-    }
-    __syncthreads();
-
-    for (int base = tid; base < CT * P * CN_VT; base += 256) {
-        int v = base % CN_VT;
-        int p = (base / CN_VT) % P;
-        int c = base / (CN_VT * P);
-        if (v >= VT) continue;
-        float zv = corr[((size_t)c * P + p) * CN_VT + v];
-        if (mode == 0)
-            zOut[((c0 + c) * zstride + (s * P + p)) * VB + v0 + v] =
-                (bf16_t)zv;
-        else
-            fOut[((c0 + c) * E + (s * P + p)) * VB + v0 + v] = zv;
-    }
-}
 
 // ===========================================================================
 // k_corr_norm_dot2: the v_dot2c_f32_bf16 form of the corr stage.
-// ISA evidence for the classic kernel (77 s_waitcnt per 64 ds_read_b128 +
-// 128 v_pk_fma_f32 in the unrolled k-loop): the wave stalls on nearly
+// ISA evidence for the pk_fma kernel it replaced (77 s_waitcnt per 64
+// ds_read_b128 + 128 v_pk_fma_f32 in the unrolled k-loop, fp32 A tile,
+// 16-voxel c-tile): the wave stalls on nearly
 // every LDS read and pays 8 b128 broadcasts per 32 MACs.  Here the A tile
 // stays bf16 (its source dtype) in k-pair-interleaved layout
 // [p][k/2][c][2], so one ds_read_b128 feeds FOUR c-columns x k-pair and
@@ -456,121 +321,20 @@ __global__ __launch_bounds__(256) void k_corr_norm_dot2(
 }
 
 // ===========================================================================
-// k_corr_norm_dot3: thread-owns-all-epochs form (P <= 4).
+// k_corr_norm_dot3s: thread-owns-all-epochs form (P <= 4) with the A
+// operand read through the SCALAR path.
 // The dot2 kernel's (chalf,p,v)->normalize->(c,v) split forces the fp32
 // corr tile through LDS (the 4 epochs of one (c,v) column live in 4
 // different waves).  Here ONE thread owns (v, all P epochs): it dots,
 // Fisher-z's, z-scores and stores each c's column entirely in
-// registers — no corr LDS tile (4 KB a-tile only -> max occupancy),
-// no inter-stage barrier, one batched store pass.
-// ===========================================================================
-#define C3_VT 256
-
-template <int TP, int TL, int C3_CT>
-__global__ __launch_bounds__(256) void k_corr_norm_dot3(
-    const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
-    bf16_t* __restrict__ zOut, ll E, ll Lrt, ll VA, ll VB, ll s0,
-    ll C, int Prt, int mode, ll zstride) {
-    static_assert(TL % 2 == 0 && TP >= 2 && TP <= 4,
-                  "dot3 kernel: even L, P in {2,4}");
-    constexpr int P = TP;
-    constexpr int KP = TL / 2;
-    const ll L = TL;
-    (void)Lrt; (void)Prt;
-    const ll nSubj = E / P;
-    const ll cTiles = (C + C3_CT - 1) / C3_CT;
-    ll b = blockIdx.x;
-    const ll vTiles = (VB + C3_VT - 1) / C3_VT;
-    const ll vt = b % vTiles; b /= vTiles;
-    const ll s = b % nSubj;   b /= nSubj;
-    const ll ct = b;
-    if (ct >= cTiles) return;
-    const ll c0 = ct * C3_CT;
-    const int CT = (int)min((ll)C3_CT, C - c0);
-    const ll v = vt * (ll)C3_VT + threadIdx.x;
-    const int tid = threadIdx.x;
-
-    // a_tile [c][kp][p][2] bf16: one bf16x8 broadcast per (c, kp)
-    // yields the k-pair for all four epochs
-    __shared__ bf16_t a_tile[C3_CT][KP][4][2];
-    for (int idx = tid; idx < C3_CT * KP * P; idx += 256) {
-        int p = idx % P;
-        int kp = (idx / P) % KP;
-        int c = idx / (P * KP);
-        #pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2) {
-            bf16_t val = (bf16_t)0.0f;
-            if (c < CT)
-                val = A[((ll)(s * P + p) * L + 2 * kp + i2) * VA
-                        + (s0 + c0 + c)];
-            a_tile[c][kp][p][i2] = val;
-        }
-    }
-    __syncthreads();
-    if (v >= VB) return;
-
-    // this thread's B columns for all P epochs (source-dtype bf16)
-    bf16x2_t bp[P][KP];
-    #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const bf16_t* brow = B + ((ll)(s * P + p) * L) * VB + v;
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp) {
-            bf16x2_t t;
-            t[0] = *(const __bf16*)&brow[(ll)(2 * kp) * VB];
-            t[1] = *(const __bf16*)&brow[(ll)(2 * kp + 1) * VB];
-            bp[p][kp] = t;
-        }
-    }
-
-    for (int c = 0; c < CT; ++c) {
-        float acc[P];
-        #pragma unroll
-        for (int p = 0; p < P; ++p) acc[p] = 0.f;
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp) {
-            bf16x8 raw = *(const bf16x8*)&a_tile[c][kp][0][0];
-            #pragma unroll
-            for (int p = 0; p < P; ++p) {
-                short2_t s2 = {raw[2 * p], raw[2 * p + 1]};
-                acc[p] = __builtin_amdgcn_fdot2_f32_bf16(
-                    __builtin_bit_cast(bf16x2_t, s2), bp[p][kp],
-                    acc[p], false);
-            }
-        }
-        float z[P];
-        float mean = 0.f, sq = 0.f;
-        #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            z[p] = fisher_z_unscaled(acc[p]);
-            mean += z[p]; sq += z[p] * z[p];
-        }
-        mean /= (float)P;
-        float var = sq / (float)P - mean * mean;
-        float inv = (var <= 0.f) ? 0.f : rsqrtf(var);
-        if (mode == 3) {
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                if (zstride < 0)
-                    zOut[(size_t)tid] = (bf16_t)((z[p] - mean) * inv);
-        } else {
-            bf16_t* dst = zOut
-                + ((c0 + c) * zstride + s * (ll)P) * VB + v;
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                dst[(size_t)p * VB] = (bf16_t)((z[p] - mean) * inv);
-        }
-    }
-}
-
-// ===========================================================================
-// k_corr_norm_dot3s: dot3 with the A operand read through the SCALAR
-// path.  In dot3 every lane of a wave reads the same a-pair (c and s
-// are wave-uniform), so the A tile belongs in SGPRs via the constant
+// registers.  Every lane of a wave reads the same a-pair (c and s are
+// wave-uniform), so the A tile belongs in SGPRs via the constant
 // cache, not in LDS: the host passes At = A[:, :, start:start+count]
 // transposed to [count, E, L] (contiguous per voxel), and the kernel
 // needs NO LDS, NO staging loop and NO barrier at all.
 // ===========================================================================
+#define C3_VT 256
+
 template <int TP, int TL, int C3_CT, typename OT = bf16_t,
           bool RAW = false>
 __device__ __forceinline__ void dot3s_body(
@@ -671,269 +435,6 @@ __global__ __launch_bounds__(256) void k_corr_norm_dot3s(
     ll C, int mode, ll zstride) {
     dot3s_body<TP, TL, C3_CT, OT, RAW>(blockIdx.x, At, B, zOut, E, VB,
                                        C, mode, zstride);
-}
-
-// ===========================================================================
-// k_corr_norm_dot3p: dot3s + software-pipelined SCALAR A prefetch.
-// The dot3s c-loop re-loads its wave-uniform A row (P*L bf16 through
-// the constant cache) at the top of every iteration and the compiler
-// parks the wave on that s_load before any MAC issues (PMC: 45 %
-// WAIT_INST, 26 % issue).  Here iteration c+1's A row streams into an
-// alternate register set WHILE c's dot chain and normalize run, so the
-// scalar-load latency hides under compute.
-// ===========================================================================
-template <int TP, int TL, int C3_CT, typename OT = bf16_t>
-__global__ __launch_bounds__(256) void k_corr_norm_dot3p(
-    const bf16_t* __restrict__ At, const bf16_t* __restrict__ B,
-    OT* __restrict__ zOut, ll E, ll VB,
-    ll C, int mode, ll zstride) {
-    static_assert(TL % 2 == 0 && TP >= 2 && TP <= 4,
-                  "dot3p kernel: even L, P in {2,4}");
-    constexpr int P = TP;
-    constexpr int KP = TL / 2;
-    constexpr int L = TL;
-    const ll nSubj = E / P;
-    const ll cTiles = (C + C3_CT - 1) / C3_CT;
-    ll b = blockIdx.x;
-    const ll vTiles = (VB + C3_VT - 1) / C3_VT;
-    const ll vt = b % vTiles; b /= vTiles;
-    const ll s = b % nSubj;   b /= nSubj;
-    const ll ct = b;
-    if (ct >= cTiles) return;
-    const ll c0 = ct * C3_CT;
-    const int CT = (int)min((ll)C3_CT, C - c0);
-    const ll v = vt * (ll)C3_VT + threadIdx.x;
-    if (v >= VB) return;
-
-    bf16x2_t bp[P][KP];
-    #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const bf16_t* brow = B + ((ll)(s * P + p) * L) * VB + v;
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp) {
-            bf16x2_t t;
-            t[0] = *(const __bf16*)&brow[(ll)(2 * kp) * VB];
-            t[1] = *(const __bf16*)&brow[(ll)(2 * kp + 1) * VB];
-            bp[p][kp] = t;
-        }
-    }
-
-    const unsigned int* abase = (const unsigned int*)
-        (At + (c0 * (ll)E + s * (ll)P) * L);
-    const int cstride = (E * L) / 2;          // dwords per voxel
-
-    unsigned int a_cur[P][KP], a_nxt[P][KP];
-    #pragma unroll
-    for (int p = 0; p < P; ++p)
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp)
-            a_cur[p][kp] = abase[p * (L / 2) + kp];
-
-    for (int c = 0; c < CT; ++c) {
-        // issue c+1's scalar loads before any use of c's values
-        if (c + 1 < CT) {
-            const unsigned int* an = abase + (ll)(c + 1) * cstride;
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                #pragma unroll
-                for (int kp = 0; kp < KP; ++kp)
-                    a_nxt[p][kp] = an[p * (L / 2) + kp];
-        }
-        float acc[P];
-        #pragma unroll
-        for (int p = 0; p < P; ++p) acc[p] = 0.f;
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp)
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                acc[p] = __builtin_amdgcn_fdot2_f32_bf16(
-                    __builtin_bit_cast(bf16x2_t, a_cur[p][kp]),
-                    bp[p][kp], acc[p], false);
-        float z[P];
-        float mean = 0.f, sq = 0.f;
-        #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            z[p] = fisher_z_unscaled(acc[p]);
-            mean += z[p]; sq += z[p] * z[p];
-        }
-        mean /= (float)P;
-        float var = sq / (float)P - mean * mean;
-        float inv = (var <= 0.f) ? 0.f : rsqrtf(var);
-        {
-            OT* dst = zOut
-                + ((c0 + c) * zstride + s * (ll)P) * VB + v;
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                dst[(size_t)p * VB] = z_cast<OT>((z[p] - mean) * inv);
-        }
-        #pragma unroll
-        for (int p = 0; p < P; ++p)
-            #pragma unroll
-            for (int kp = 0; kp < KP; ++kp)
-                a_cur[p][kp] = a_nxt[p][kp];
-    }
-}
-
-// ===========================================================================
-// k_corr_norm_mfma: the MFMA form of k_corr_norm for L <= 32.
-// PMC evidence (profiles/README.md): the VALU form is issue-bound at
-// ~5 instructions per useful FMA; one v_mfma_f32_16x16x32_bf16 computes a
-// full 16c x 16v correlation tile (K = L padded to 32) in ONE instruction.
-//   A fragment: a_tile [P][16 c][32 k] bf16 — lane reads 8 contiguous
-//     bf16 at [c = l%16][k0 = 8*(l>>4)] → one ds_read_b128.
-//   B fragment: b_tile [P][VT v][32 k] (+pad) — same read shape.
-// b_tile is staged v-coalesced from global and transposed into k-rows
-// during the write (row pad +2 keeps the writes conflict-free).
-// ===========================================================================
-#define CM_CT 16
-#define CM_VT 64
-#define CM_K 32
-#define CM_BPAD 2
-#define CM_BROW (CM_K + CM_BPAD)
-
-template <int TP, int TL>
-__global__ __launch_bounds__(256) void k_corr_norm_mfma(
-    const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
-    bf16_t* __restrict__ zOut, float* __restrict__ fOut,
-    ll E, ll Lrt, ll VA, ll VB, ll s0, ll C, int Prt, int mode,
-    ll zstride) {
-    static_assert(TL <= CM_K, "MFMA corr kernel requires L <= 32");
-    const int P = TP > 0 ? TP : Prt;
-    const ll L = TL;
-    (void)Lrt;
-    const ll nSubj = E / P;
-    const ll cTiles = (C + CM_CT - 1) / CM_CT;
-    const ll vTiles = (VB + CM_VT - 1) / CM_VT;
-    ll b = blockIdx.x;
-    const ll vt = b % vTiles; b /= vTiles;
-    const ll s = b % nSubj;   b /= nSubj;
-    const ll ct = b;
-    if (ct >= cTiles) return;
-
-    const ll c0 = ct * CM_CT;
-    const ll v0 = vt * CM_VT;
-    const int CT = (int)min((ll)CM_CT, C - c0);
-    const int VT = (int)min((ll)CM_VT, VB - v0);
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;          // 4 waves
-
-    extern __shared__ char smem[];
-    // a_tile [P][CM_CT][CM_K] bf16, b_tile [P][CM_VT][CM_BROW] bf16,
-    // corr [CM_CT][P][CM_VT] fp32
-    bf16_t* a_tile = (bf16_t*)smem;
-    bf16_t* b_tile = a_tile + (size_t)P * CM_CT * CM_K;
-    float* corr = (float*)(b_tile + (size_t)P * CM_VT * CM_BROW);
-
-    // --- stage A transposed: a_tile[p][c][k] (zero-padded k >= L)
-    for (int idx = tid; idx < P * CM_CT * CM_K; idx += 256) {
-        int k = idx % CM_K;
-        int c = (idx / CM_K) % CM_CT;
-        int p = idx / (CM_K * CM_CT);
-        bf16_t val = (bf16_t)0.0f;
-        if (c < CT && k < (int)L)
-            val = A[((s * P + p) * L + k) * VA + (s0 + c0 + c)];
-        a_tile[idx] = val;
-    }
-    // --- stage B transposed: b_tile[p][v][k]; global reads coalesced
-    // over v (64 lanes = one 128B line per (p, k))
-    {
-        int v = tid & 63;
-        for (int pk = tid >> 6; pk < P * CM_K; pk += 4) {
-            int k = pk % CM_K;
-            int p = pk / CM_K;
-            bf16_t val = (bf16_t)0.0f;
-            if (k < (int)L && v < VT)
-                val = B[((s * P + p) * L + k) * VB + (v0 + v)];
-            b_tile[((size_t)p * CM_VT + v) * CM_BROW + k] = val;
-        }
-    }
-    __syncthreads();
-
-    // --- MFMA: 16 (p, v-subtile) units over 4 waves
-    const int frow = lane & 15;
-    const int fk = 8 * (lane >> 4);
-    const int dcol = lane & 15;            // v within subtile
-    const int drow4 = (lane >> 4) * 4;     // c base
-    const int units = P * (CM_VT / 16);
-    for (int u = wid; u < units; u += 4) {
-        int p = u / (CM_VT / 16);
-        int vsub = u % (CM_VT / 16);
-        bf16x8 fa = *(const bf16x8*)&a_tile[((size_t)p * CM_CT + frow)
-                                            * CM_K + fk];
-        bf16x8 fb = *(const bf16x8*)&b_tile[
-            ((size_t)p * CM_VT + vsub * 16 + frow) * CM_BROW + fk];
-        f32x4 acc = (f32x4)0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc,
-                                                      0, 0, 0);
-        // D: row = c = drow4 + r, col = v = dcol
-        #pragma unroll
-        for (int r = 0; r < 4; ++r)
-            corr[((size_t)(drow4 + r) * P + p) * CM_VT
-                 + vsub * 16 + dcol] = acc[r];
-    }
-    __syncthreads();
-
-    if (mode == 2) {
-        for (int base = tid; base < CT * P * CM_VT; base += 256) {
-            int v = base % CM_VT;
-            int p = (base / CM_VT) % P;
-            int c = base / (CM_VT * P);
-            if (v < VT)
-                fOut[((c0 + c) * E + (s * P + p)) * VB + v0 + v] =
-                    corr[((size_t)c * P + p) * CM_VT + v];
-        }
-        return;
-    }
-
-    // --- normalization (identical to the VALU kernel)
-    for (int base = tid; base < CT * CM_VT; base += 256) {
-        int v = base % CM_VT;
-        int c = base / CM_VT;
-        if (v >= VT) continue;
-        float* col = corr + ((size_t)c * P) * CM_VT + v;
-        float mean = 0.f, sq = 0.f;
-        if (TP > 0) {
-            float z[TP > 0 ? TP : 1];
-            #pragma unroll
-            for (int p = 0; p < P; ++p) {
-                z[p] = fisher_z(col[(size_t)p * CM_VT]);
-                mean += z[p]; sq += z[p] * z[p];
-            }
-            mean /= (float)P;
-            float var = sq / (float)P - mean * mean;
-            float inv = (var <= 0.f) ? 0.f : rsqrtf(var);
-            #pragma unroll
-            for (int p = 0; p < P; ++p)
-                col[(size_t)p * CM_VT] = (z[p] - mean) * inv;
-        } else {
-            for (int p = 0; p < P; ++p) {
-                float zv = fisher_z(col[(size_t)p * CM_VT]);
-                mean += zv; sq += zv * zv;
-                col[(size_t)p * CM_VT] = zv;
-            }
-            mean /= (float)P;
-            float var = sq / (float)P - mean * mean;
-            float inv = (var <= 0.f) ? 0.f : rsqrtf(var);
-            for (int p = 0; p < P; ++p)
-                col[(size_t)p * CM_VT] = (col[(size_t)p * CM_VT] - mean)
-                                         * inv;
-        }
-    }
-    __syncthreads();
-
-    for (int base = tid; base < CT * P * CM_VT; base += 256) {
-        int v = base % CM_VT;
-        int p = (base / CM_VT) % P;
-        int c = base / (CM_VT * P);
-        if (v >= VT) continue;
-        float zv = corr[((size_t)c * P + p) * CM_VT + v];
-        if (mode == 0)
-            zOut[((c0 + c) * zstride + (s * P + p)) * VB + v0 + v] =
-                (bf16_t)zv;
-        else
-            fOut[((c0 + c) * E + (s * P + p)) * VB + v0 + v] = zv;
-    }
 }
 
 // ===========================================================================
@@ -1109,38 +610,6 @@ __global__ __launch_bounds__(512) void k_fused_corr_gram(
                 }
                 ++t;
             }
-    }
-}
-
-extern "C" int fcma_fused_gram_supported(ll E, int P, ll L) {
-    return E == 64 && P == 4 && L > 0 && L % 2 == 0 && L <= CN_MAXL;
-}
-
-template <int TL>
-static void launch_fused_t(const void* A, const void* B, float* Gpart,
-                           ll VA, ll VB, ll s0, ll C, int nsplit,
-                           hipStream_t stream) {
-    ll grid = ((C + FG_CB - 1) / FG_CB) * nsplit;
-    hipLaunchKernelGGL((k_fused_corr_gram<TL>), dim3(grid), dim3(512),
-                       0, stream, (const bf16_t*)A, (const bf16_t*)B,
-                       Gpart, VA, VB, s0, C, nsplit);
-}
-
-extern "C" void launch_fcma_fused_corr_gram(
-    const void* A, const void* B, float* Gpart, ll L, ll VA, ll VB,
-    ll s0, ll C, int nsplit, hipStream_t stream) {
-    switch (L) {
-        case 8:  launch_fused_t<8>(A, B, Gpart, VA, VB, s0, C, nsplit,
-                                   stream); break;
-        case 16: launch_fused_t<16>(A, B, Gpart, VA, VB, s0, C, nsplit,
-                                   stream); break;
-        case 24: launch_fused_t<24>(A, B, Gpart, VA, VB, s0, C, nsplit,
-                                   stream); break;
-        case 32: launch_fused_t<32>(A, B, Gpart, VA, VB, s0, C, nsplit,
-                                   stream); break;
-        case 40: launch_fused_t<40>(A, B, Gpart, VA, VB, s0, C, nsplit,
-                                   stream); break;
-        default: break;
     }
 }
 
@@ -1664,10 +1133,54 @@ __global__ __launch_bounds__(256) void k_gram_f32(
 }
 
 // ===========================================================================
-// host-side launchers (P-templated dispatch)
+// host-side launchers
 // ===========================================================================
 
 static inline ll ceil_div(ll a, ll b) { return (a + b - 1) / b; }
+
+// The corr kernels' compile-time epoch lengths, written once: the host
+// pads L up to the next entry (zero rows are inert for z-scored epochs).
+constexpr int kSupportedL[] = {8, 12, 16, 20, 24, 28, 32, 36, 40};
+// k_fused_corr_gram is instantiated for these only
+constexpr int kFusedL[] = {8, 16, 24, 32, 40};
+
+extern "C" ll fcma_supported_L(ll L) {
+    for (int opt : kSupportedL)
+        if (L <= opt) return opt;
+    return -1;
+}
+
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// Runtime L -> compile-time TL: calls f(int_c<TL>{}) for the entry of
+// Ls equal to L; false (and no call) when there is none.
+template <auto& Ls, class F, size_t... I>
+static bool dispatch_l(ll L, F&& f, std::index_sequence<I...>) {
+    return ((L == Ls[I] && (f(int_c<Ls[I]>{}), true)) || ...);
+}
+
+template <auto& Ls, class F>
+static bool dispatch_l(ll L, F&& f) {
+    return dispatch_l<Ls>(L, f, std::make_index_sequence<std::size(Ls)>{});
+}
+
+template <int TP, class F>
+static bool dispatch_pl_at(ll L, F& f) {
+    return dispatch_l<kSupportedL>(L, [&](auto tl) { f(int_c<TP>{}, tl); });
+}
+
+// Runtime (P, L) -> compile-time (TP, TL): calls f(int_c<TP>{},
+// int_c<TL>{}) for the first entry of Ps that is P, or that is 0 (the
+// kernels' runtime-P instantiation, which takes every P), and for L in
+// kSupportedL.  Returns false, with nothing called, when (P, L) has no
+// instantiation — the launchers hand that to their caller.
+template <int... Ps, class F>
+static bool dispatch_pl(int P, ll L, F&& f) {
+    bool hit = false;
+    (void)(((Ps == 0 || P == Ps)
+            && (hit = dispatch_pl_at<Ps>(L, f), true)) || ...);
+    return hit;
+}
 
 template <int TP>
 static void launch_normalize_t(float* corr, ll C, ll E, ll V, int P,
@@ -1690,239 +1203,163 @@ extern "C" void launch_fcma_normalize(float* corr, ll C, ll E, ll V, int P,
     }
 }
 
-// runtime corr-kernel selector for within-probe A/B
-// (BRAINIAK_CORR_KERNEL=classic forces the pk_fma form)
-static int corr_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("BRAINIAK_CORR_KERNEL");
-        v = 3;   // scalar-A dot3s where applicable (12.9 ms/step
-                 // no-cv vs dot3 13.6 / dot2 16.5 — profiles/README.md)
-        if (e && strcmp(e, "classic") == 0) v = 0;
-        if (e && strcmp(e, "dot2") == 0) v = 1;
-        if (e && strcmp(e, "dot3") == 0) v = 2;
-        if (e && strcmp(e, "dot3s") == 0) v = 3;
-        if (e && strcmp(e, "dot3p") == 0) v = 4;
-    }
-    return v;
-}
-
 // host mirror of the dot2 kernel's TCT constexpr
 static ll dot2_ct(int P) {
     return (P == 2 || P == 4) ? 32 : CN_CT;
 }
 
+// dynamic LDS of k_corr_norm_dot2: bf16 a_tile + fp32 corr tile
+extern "C" int fcma_corr_norm_smem(ll L, int P) {
+    ll ct = dot2_ct(P);
+    size_t smem = (size_t)P * L * ct * sizeof(bf16_t)
+                + (size_t)ct * P * CN_VT * sizeof(float);
+    return (int)smem;
+}
+
+// The dispatch rule of the corr(+normalize) stage, in one place:
+//   mode 0 (bf16 Z), At given, P in {2,4} -> k_corr_norm_dot3s<TP,TL,128>
+//     (12.9 ms/step no-cv vs 16.5 for dot2 — profiles/README.md)
+//   everything else                        -> k_corr_norm_dot2<TP,TL>
 template <int TP, int TL>
 static void launch_corr_norm_t(const void* A, const void* B, void* zOut,
                                float* fOut, ll E, ll L, ll VA, ll VB,
                                ll s0, ll C, int P, int mode, ll zstride,
-                               size_t smem, hipStream_t stream,
-                               const void* At = nullptr) {
+                               hipStream_t stream, const void* At) {
     ll nSubj = E / P;
-    // Measured A/B on MI355X (profiles/README.md): the VALU form at
-    // 2.09 ms/512-voxel call beats the MFMA form (3.86 ms) — with
-    // K = L <= 32 the MFMA phase is 16 instructions per block and the
-    // kernel is bound by staging/normalize/write address arithmetic
-    // (PMC: MFMA form = 1.43x the VALU instructions).  Set USE_MFMA_CORR
-    // to re-enable the MFMA path when its staging is restructured.
-#ifdef USE_MFMA_CORR
-    if constexpr (TL <= CM_K) {
-        size_t smem_mfma = (size_t)P * CM_CT * CM_K * sizeof(bf16_t)
-                         + (size_t)P * CM_VT * CM_BROW * sizeof(bf16_t)
-                         + (size_t)CM_CT * P * CM_VT * sizeof(float);
-        ll grid = ceil_div(C, CM_CT) * nSubj * ceil_div(VB, CM_VT);
-        hipLaunchKernelGGL((k_corr_norm_mfma<TP, TL>), dim3(grid),
-                           dim3(256), smem_mfma, stream,
-                           (const bf16_t*)A, (const bf16_t*)B,
-                           (bf16_t*)zOut, fOut, E, L, VA, VB, s0, C, P,
-                           mode, zstride);
-        return;
-    }
-#endif
-    if (corr_variant() >= 3 && At != nullptr && (TL % 2) == 0
-        && mode != 1 && mode != 2 && (TP == 2 || TP == 4)) {
-        if constexpr (TL % 2 == 0 && TP >= 2 && TP <= 4) {
+    if constexpr (TP == 2 || TP == 4) {
+        if (mode == 0 && At != nullptr) {
             ll grid3 = ceil_div(C, 128) * nSubj * ceil_div(VB, C3_VT);
-            if (corr_variant() == 4)
-                hipLaunchKernelGGL((k_corr_norm_dot3p<TP, TL, 128>),
-                                   dim3(grid3), dim3(256), 0, stream,
-                                   (const bf16_t*)At, (const bf16_t*)B,
-                                   (bf16_t*)zOut, E, VB, C, mode,
-                                   zstride);
-            else
-                hipLaunchKernelGGL((k_corr_norm_dot3s<TP, TL, 128>),
-                                   dim3(grid3), dim3(256), 0, stream,
-                                   (const bf16_t*)At, (const bf16_t*)B,
-                                   (bf16_t*)zOut, E, VB, C, mode,
-                                   zstride);
+            hipLaunchKernelGGL((k_corr_norm_dot3s<TP, TL, 128>),
+                               dim3(grid3), dim3(256), 0, stream,
+                               (const bf16_t*)At, (const bf16_t*)B,
+                               (bf16_t*)zOut, E, VB, C, mode, zstride);
             return;
         }
     }
-    if (corr_variant() >= 2 && (TL % 2) == 0 && mode != 1 && mode != 2
-        && (TP == 2 || TP == 4)) {
-        if constexpr (TL % 2 == 0 && TP >= 2 && TP <= 4) {
-            static int ct3 = -1;
-            if (ct3 < 0) {
-                const char* e = getenv("BRAINIAK_DOT3_CT");
-                // measured sweep (profiles/README.md): 32 -> 15.1,
-                // 64 -> 13.8, 128 -> 13.2, 256 -> 12.9, 512 -> 14.1
-                // ms/step no-cv; 128 and 256 tie on the full step,
-                // 128 keeps more blocks in flight for small shards
-                ct3 = e ? atoi(e) : 128;
-                if (ct3 != 32 && ct3 != 64 && ct3 != 256 && ct3 != 512)
-                    ct3 = 128;
-            }
-            ll grid3 = ceil_div(C, ct3) * nSubj * ceil_div(VB, C3_VT);
-            if (ct3 == 64)
-                hipLaunchKernelGGL((k_corr_norm_dot3<TP, TL, 64>),
-                                   dim3(grid3), dim3(256), 0, stream,
-                                   (const bf16_t*)A, (const bf16_t*)B,
-                                   (bf16_t*)zOut, E, L, VA, VB, s0, C,
-                                   P, mode, zstride);
-            else if (ct3 == 128)
-                hipLaunchKernelGGL((k_corr_norm_dot3<TP, TL, 128>),
-                                   dim3(grid3), dim3(256), 0, stream,
-                                   (const bf16_t*)A, (const bf16_t*)B,
-                                   (bf16_t*)zOut, E, L, VA, VB, s0, C,
-                                   P, mode, zstride);
-            else if (ct3 == 512)
-                hipLaunchKernelGGL((k_corr_norm_dot3<TP, TL, 512>),
-                                   dim3(grid3), dim3(256), 0, stream,
-                                   (const bf16_t*)A, (const bf16_t*)B,
-                                   (bf16_t*)zOut, E, L, VA, VB, s0, C,
-                                   P, mode, zstride);
-            else if (ct3 == 256)
-                hipLaunchKernelGGL((k_corr_norm_dot3<TP, TL, 256>),
-                                   dim3(grid3), dim3(256), 0, stream,
-                                   (const bf16_t*)A, (const bf16_t*)B,
-                                   (bf16_t*)zOut, E, L, VA, VB, s0, C,
-                                   P, mode, zstride);
-            else
-                hipLaunchKernelGGL((k_corr_norm_dot3<TP, TL, 32>),
-                                   dim3(grid3), dim3(256), 0, stream,
-                                   (const bf16_t*)A, (const bf16_t*)B,
-                                   (bf16_t*)zOut, E, L, VA, VB, s0, C,
-                                   P, mode, zstride);
-            return;
+    size_t smem = (size_t)fcma_corr_norm_smem(L, P);
+    ll gridd = ceil_div(C, dot2_ct(P)) * nSubj * ceil_div(VB, CN_VT);
+    if (smem > 64 * 1024) {
+        // gfx950 has 160 KB LDS but dynamic allocations above the
+        // 64 KB default need the explicit opt-in, once per kernel
+        static bool raised = false;
+        if (!raised) {
+            (void)hipFuncSetAttribute(
+                reinterpret_cast<const void*>(
+                    &k_corr_norm_dot2<TP, TL>),
+                hipFuncAttributeMaxDynamicSharedMemorySize,
+                160 * 1024);
+            raised = true;
         }
     }
-    if (corr_variant() >= 1 && (TL % 2) == 0) {
-        ll gridd = ceil_div(C, dot2_ct(P)) * nSubj * ceil_div(VB, CN_VT);
-        if (smem > 64 * 1024) {
-            // gfx950 has 160 KB LDS but dynamic allocations above the
-            // 64 KB default need the explicit opt-in, once per kernel
-            static bool raised = false;
-            if (!raised) {
-                (void)hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(
-                        &k_corr_norm_dot2<TP, TL>),
-                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                    160 * 1024);
-                raised = true;
-            }
-        }
-        hipLaunchKernelGGL((k_corr_norm_dot2<TP, TL>), dim3(gridd),
-                           dim3(256), smem, stream, (const bf16_t*)A,
-                           (const bf16_t*)B, (bf16_t*)zOut, fOut, E, L,
-                           VA, VB, s0, C, P, mode, zstride);
-        return;
-    }
-    ll grid = ceil_div(C, CN_CT) * nSubj * ceil_div(VB, CN_VT);
-    hipLaunchKernelGGL((k_corr_norm<TP, TL>), dim3(grid), dim3(256),
-                       smem, stream, (const bf16_t*)A,
+    hipLaunchKernelGGL((k_corr_norm_dot2<TP, TL>), dim3(gridd),
+                       dim3(256), smem, stream, (const bf16_t*)A,
                        (const bf16_t*)B, (bf16_t*)zOut, fOut, E, L,
                        VA, VB, s0, C, P, mode, zstride);
 }
 
-extern "C" int fcma_corr_variant(void) { return corr_variant(); }
-
-extern "C" int fcma_corr_norm_smem(ll L, int P) {
-#ifdef USE_MFMA_CORR
-    if (L <= CM_K) {
-        size_t smem = (size_t)P * CM_CT * CM_K * sizeof(bf16_t)
-                    + (size_t)P * CM_VT * CM_BROW * sizeof(bf16_t)
-                    + (size_t)CM_CT * P * CM_VT * sizeof(float);
-        return (int)smem;
-    }
-#endif
-    if (corr_variant() >= 1 && (L % 2) == 0) {
-        ll ct = dot2_ct(P);
-        size_t smem = (size_t)P * L * ct * sizeof(bf16_t)   // bf16 a
-                    + (size_t)ct * P * CN_VT * sizeof(float);
-        return (int)smem;
-    }
-    size_t smem = (size_t)P * L * CN_CT * sizeof(float)   // fp32 a_tile
-                + (size_t)CN_CT * P * CN_VT * sizeof(float);
-    return (int)smem;
+// The four (P, L)-templated launchers return 1, or 0 when (P, L) has no
+// instantiation and nothing was launched.
+extern "C" int launch_fcma_corr_norm(const void* A, const void* B,
+                                     void* zOut, float* fOut, ll E, ll L,
+                                     ll VA, ll VB, ll s0, ll C, int P,
+                                     int mode, ll zstride,
+                                     hipStream_t stream, const void* At) {
+    return dispatch_pl<2, 4, 8, 16, 0>(P, L, [&](auto tp, auto tl) {
+        launch_corr_norm_t<decltype(tp)::value, decltype(tl)::value>(
+            A, B, zOut, fOut, E, L, VA, VB, s0, C, P, mode, zstride,
+            stream, At);
+    });
 }
 
-template <int TL>
-static void dispatch_p(const void* A, const void* B, void* zOut,
-                       float* fOut, ll E, ll L, ll VA, ll VB, ll s0, ll C,
-                       int P, int mode, ll zstride, size_t smem,
-                       hipStream_t stream, const void* At = nullptr) {
-    switch (P) {
-        case 2:  launch_corr_norm_t<2, TL>(A, B, zOut, fOut, E, L, VA, VB,
-                                           s0, C, P, mode, zstride,
-                                           smem, stream, At);
-                 break;
-        case 4:  launch_corr_norm_t<4, TL>(A, B, zOut, fOut, E, L, VA, VB,
-                                           s0, C, P, mode, zstride,
-                                           smem, stream, At);
-                 break;
-        case 8:  launch_corr_norm_t<8, TL>(A, B, zOut, fOut, E, L, VA, VB,
-                                           s0, C, P, mode, zstride,
-                                           smem, stream);
-                 break;
-        case 16: launch_corr_norm_t<16, TL>(A, B, zOut, fOut, E, L, VA, VB,
-                                           s0, C, P, mode, zstride,
-                                           smem, stream);
-                 break;
-        default: launch_corr_norm_t<0, TL>(A, B, zOut, fOut, E, L, VA, VB,
-                                           s0, C, P, mode, zstride,
-                                           smem, stream);
-                 break;
-    }
+// raw-r variant: dot3s with the normalize deferred (bf16 Z only)
+extern "C" int launch_fcma_corr_raw(const void* At, const void* B,
+                                    void* zOut, ll E, ll L, ll VB,
+                                    ll C, ll zstride, int P,
+                                    hipStream_t stream) {
+    ll nSubj = E / P;
+    ll grid3 = ceil_div(C, 128) * nSubj * ceil_div(VB, C3_VT);
+    return dispatch_pl<2, 4>(P, L, [&](auto tp, auto tl) {
+        constexpr int TP = decltype(tp)::value, TL = decltype(tl)::value;
+        hipLaunchKernelGGL((k_corr_norm_dot3s<TP, TL, 128, bf16_t, true>),
+                           dim3(grid3), dim3(256), 0, stream,
+                           (const bf16_t*)At, (const bf16_t*)B,
+                           (bf16_t*)zOut, E, VB, C, /*mode=*/0, zstride);
+    });
 }
 
-// host pads L to one of these (zero rows are inert for z-scored epochs)
-extern "C" ll fcma_supported_L(ll L) {
-    const ll opts[9] = {8, 12, 16, 20, 24, 28, 32, 36, 40};
-    for (int i = 0; i < 9; ++i)
-        if (L <= opts[i]) return opts[i];
-    return -1;
+// fp8-output corr+normalize: the dot3s kernel with an e4m3 Z store.
+// P in {2, 4}, even L (the production dot3s envelope); At required.
+extern "C" int fcma_corr_norm_z8_supported(ll E, int P, ll L) {
+    return (P == 2 || P == 4) && (L % 2) == 0 && (E % P) == 0;
 }
 
-extern "C" void launch_fcma_corr_norm(const void* A, const void* B,
-                                      void* zOut, float* fOut, ll E, ll L,
-                                      ll VA, ll VB, ll s0, ll C, int P,
-                                      int mode, ll zstride,
-                                      hipStream_t stream,
-                                      const void* At) {
-    static int probe_mode3 = getenv("BRAINIAK_CORR_MODE3") ? 1 : 0;
-    if (probe_mode3 && mode == 0 && corr_variant() >= 1) mode = 3;
-    size_t smem = (size_t)fcma_corr_norm_smem(L, P);
-    switch (L) {
-        case 8:  dispatch_p<8>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 12: dispatch_p<12>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 20: dispatch_p<20>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 28: dispatch_p<28>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 36: dispatch_p<36>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 16: dispatch_p<16>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 24: dispatch_p<24>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 32: dispatch_p<32>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        case 40: dispatch_p<40>(A, B, zOut, fOut, E, L, VA, VB, s0, C, P,
-                               mode, zstride, smem, stream, At); break;
-        default: break;  // host guarantees L in the supported set
-    }
+extern "C" int launch_fcma_corr_norm_z8(const void* At, const void* B,
+                                        void* zOut, ll E, ll L, ll VB,
+                                        ll C, ll zstride,
+                                        int P, hipStream_t stream) {
+    ll nSubj = E / P;
+    ll grid3 = ceil_div(C, 128) * nSubj * ceil_div(VB, C3_VT);
+    return dispatch_pl<2, 4>(P, L, [&](auto tp, auto tl) {
+        constexpr int TP = decltype(tp)::value, TL = decltype(tl)::value;
+        hipLaunchKernelGGL((k_corr_norm_dot3s<TP, TL, 128, fp8_t>),
+                           dim3(grid3), dim3(256), 0, stream,
+                           (const bf16_t*)At, (const bf16_t*)B,
+                           (fp8_t*)zOut, E, VB, C, /*mode=*/0, zstride);
+    });
+}
+
+extern "C" ll fcma_duo_gram_blocks(ll Cg, ll Eg, ll nsplit) {
+    ll eb = Eg / 64;
+    return Cg * eb * eb * nsplit;
+}
+
+// duo grid: 128-voxel corr tiles (a 64-voxel tile measured 2 % slower —
+// profiles/README.md), DZ by whether the Gram has more than one band
+extern "C" int launch_fcma_corr_gram_duo(
+    const void* At, const void* B, void* zOut, ll E, ll L, ll VB, ll C,
+    ll zstride, int P,
+    const void* Zprev, float* G, ll Cg, ll Eg, ll Vg, ll nsplit,
+    const float* GpSum, float* GSumOut, ll Cs, ll nsplitSum,
+    int do_shrink, hipStream_t stream) {
+    ll nSubj = E / P;
+    ll nCorr = ceil_div(C, 128) * nSubj * ceil_div(VB, C3_VT);
+    ll nGram = (G != nullptr) ? fcma_duo_gram_blocks(Cg, Eg, nsplit)
+                              : 0;
+    ll nSum = (GSumOut != nullptr) ? Cs : 0;
+    ll grid = nCorr + nGram + nSum;
+    const bool dz = (Eg != 64);
+    return dispatch_pl<2, 4>(P, L, [&](auto tp, auto tl) {
+        constexpr int TP = decltype(tp)::value, TL = decltype(tl)::value;
+        auto launch = [&](auto dzc) {
+            constexpr bool DZ = decltype(dzc)::value;
+            hipLaunchKernelGGL((k_corr_gram_duo<TP, TL, TP, DZ, 128>),
+                               dim3(grid), dim3(256), 0, stream,
+                               (const bf16_t*)At, (const bf16_t*)B,
+                               (bf16_t*)zOut, E, VB, C, zstride,
+                               (const bf16_t*)Zprev, G, Cg, Eg, Vg,
+                               nsplit, GpSum, GSumOut, Cs, nsplitSum,
+                               do_shrink, nCorr, nGram, nSum);
+        };
+        if (dz) launch(std::true_type{});
+        else    launch(std::false_type{});
+    });
+}
+
+// single-kernel chunk path: E = 64, P = 4 and an instantiated L
+extern "C" int fcma_fused_gram_supported(ll E, int P, ll L) {
+    return E == 64 && P == 4 && dispatch_l<kFusedL>(L, [](auto) {});
+}
+
+extern "C" int launch_fcma_fused_corr_gram(
+    const void* A, const void* B, float* Gpart, ll L, ll VA, ll VB,
+    ll s0, ll C, int nsplit, hipStream_t stream) {
+    ll grid = ((C + FG_CB - 1) / FG_CB) * nsplit;
+    return dispatch_l<kFusedL>(L, [&](auto tl) {
+        hipLaunchKernelGGL((k_fused_corr_gram<decltype(tl)::value>),
+                           dim3(grid), dim3(512), 0, stream,
+                           (const bf16_t*)A, (const bf16_t*)B, Gpart, VA,
+                           VB, s0, C, nsplit);
+    });
 }
 
 extern "C" void launch_fcma_gram_bf16(const void* Z, float* G, ll C, ll E,
@@ -1959,299 +1396,6 @@ extern "C" void launch_fcma_gram_bf16_norm(const void* Z, float* G,
     #undef GRAM_NORM_CASE
 }
 
-// raw-r dot3s with TWO voxels per thread: the raw kernel is
-// memory-latency bound (PMC r2: 67 % WAIT_ANY) — doubling the
-// per-thread streams doubles outstanding B-loads/Z-stores per wave.
-template <int TP, int TL, int C3_CT>
-__global__ __launch_bounds__(256) void k_corr_raw_v2(
-    const bf16_t* __restrict__ At, const bf16_t* __restrict__ B,
-    bf16_t* __restrict__ zOut, ll E, ll VB,
-    ll C, ll zstride) {
-    static_assert(TL % 2 == 0 && TP >= 2 && TP <= 4, "even L, P 2/4");
-    constexpr int P = TP;
-    constexpr int KP = TL / 2;
-    constexpr int L = TL;
-    constexpr int VT2 = 2 * C3_VT;
-    const ll nSubj = E / P;
-    const ll cTiles = (C + C3_CT - 1) / C3_CT;
-    const ll vTiles = (VB + VT2 - 1) / VT2;
-    ll b = blockIdx.x;
-    const ll vt = b % vTiles; b /= vTiles;
-    const ll s = b % nSubj;   b /= nSubj;
-    const ll ct = b;
-    if (ct >= cTiles) return;
-    const ll c0 = ct * C3_CT;
-    const int CT = (int)min((ll)C3_CT, C - c0);
-    const ll v0 = vt * (ll)VT2 + threadIdx.x;
-    const ll v1 = v0 + C3_VT;
-    const bool has1 = v1 < VB;
-    if (v0 >= VB) return;
-
-    bf16x2_t bp0[P][KP], bp1[P][KP];
-    #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const bf16_t* brow = B + ((ll)(s * P + p) * L) * VB;
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp) {
-            bf16x2_t t0, t1;
-            t0[0] = *(const __bf16*)&brow[(ll)(2 * kp) * VB + v0];
-            t0[1] = *(const __bf16*)&brow[(ll)(2 * kp + 1) * VB + v0];
-            bp0[p][kp] = t0;
-            ll vv = has1 ? v1 : v0;
-            t1[0] = *(const __bf16*)&brow[(ll)(2 * kp) * VB + vv];
-            t1[1] = *(const __bf16*)&brow[(ll)(2 * kp + 1) * VB + vv];
-            bp1[p][kp] = t1;
-        }
-    }
-
-    const unsigned int* abase = (const unsigned int*)
-        (At + (c0 * (ll)E + s * (ll)P) * L);
-    const int cstride = (E * L) / 2;
-
-    for (int c = 0; c < CT; ++c) {
-        const unsigned int* ac = abase + (ll)c * cstride;
-        float acc0[P], acc1[P];
-        #pragma unroll
-        for (int p = 0; p < P; ++p) { acc0[p] = 0.f; acc1[p] = 0.f; }
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp)
-            #pragma unroll
-            for (int p = 0; p < P; ++p) {
-                bf16x2_t a = __builtin_bit_cast(
-                    bf16x2_t, ac[p * (L / 2) + kp]);
-                acc0[p] = __builtin_amdgcn_fdot2_f32_bf16(
-                    a, bp0[p][kp], acc0[p], false);
-                acc1[p] = __builtin_amdgcn_fdot2_f32_bf16(
-                    a, bp1[p][kp], acc1[p], false);
-            }
-        bf16_t* dst = zOut + ((c0 + c) * zstride + s * (ll)P) * VB;
-        #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            dst[(size_t)p * VB + v0] = (bf16_t)acc0[p];
-            if (has1)
-                dst[(size_t)p * VB + v1] = (bf16_t)acc1[p];
-        }
-    }
-}
-
-// raw-r dot3s with ADJACENT voxel pairs per thread: every B load and
-// Z store becomes a 4-byte (bf16x2) access — half the memory
-// instructions for the same bytes (probe: instruction-rate vs
-// byte-rate limited stores).
-template <int TP, int TL, int C3_CT>
-__global__ __launch_bounds__(256) void k_corr_raw_pair(
-    const bf16_t* __restrict__ At, const bf16_t* __restrict__ B,
-    bf16_t* __restrict__ zOut, ll E, ll VB,
-    ll C, ll zstride) {
-    static_assert(TL % 2 == 0 && TP >= 2 && TP <= 4, "even L, P 2/4");
-    constexpr int P = TP;
-    constexpr int KP = TL / 2;
-    constexpr int L = TL;
-    constexpr int VT2 = 2 * C3_VT;
-    const ll nSubj = E / P;
-    const ll cTiles = (C + C3_CT - 1) / C3_CT;
-    const ll vTiles = (VB + VT2 - 1) / VT2;
-    ll b = blockIdx.x;
-    const ll vt = b % vTiles; b /= vTiles;
-    const ll s = b % nSubj;   b /= nSubj;
-    const ll ct = b;
-    if (ct >= cTiles) return;
-    const ll c0 = ct * C3_CT;
-    const int CT = (int)min((ll)C3_CT, C - c0);
-    const ll v0 = vt * (ll)VT2 + 2 * threadIdx.x;   // adjacent pair
-    if (v0 + 1 >= VB) {
-        if (v0 >= VB) return;
-        // odd tail voxel: fall through scalar (VB is 16-padded so
-        // this branch is dead in production, kept for generality)
-    }
-
-    // B loads: one bf16x2 per (p, kp, row) covering (v0, v0+1)
-    bf16x2_t bp[P][KP][2];           // [..][2] = the two L rows
-    #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const bf16_t* brow = B + ((ll)(s * P + p) * L) * VB + v0;
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp) {
-            bp[p][kp][0] = *(const bf16x2_t*)&brow[(ll)(2 * kp) * VB];
-            bp[p][kp][1] = *(const bf16x2_t*)&brow[(ll)(2 * kp + 1)
-                                                   * VB];
-        }
-    }
-
-    const unsigned int* abase = (const unsigned int*)
-        (At + (c0 * (ll)E + s * (ll)P) * L);
-    const int cstride = (E * L) / 2;
-
-    for (int c = 0; c < CT; ++c) {
-        const unsigned int* ac = abase + (ll)c * cstride;
-        float acc0[P], acc1[P];
-        #pragma unroll
-        for (int p = 0; p < P; ++p) { acc0[p] = 0.f; acc1[p] = 0.f; }
-        #pragma unroll
-        for (int kp = 0; kp < KP; ++kp)
-            #pragma unroll
-            for (int p = 0; p < P; ++p) {
-                bf16x2_t a = __builtin_bit_cast(
-                    bf16x2_t, ac[p * (L / 2) + kp]);
-                // a = (A[2kp], A[2kp+1]); B pair rows give
-                // (B[2kp][v0], B[2kp][v0+1]) etc. — regroup:
-                bf16x2_t b0, b1;
-                b0[0] = bp[p][kp][0][0]; b0[1] = bp[p][kp][1][0];
-                b1[0] = bp[p][kp][0][1]; b1[1] = bp[p][kp][1][1];
-                acc0[p] = __builtin_amdgcn_fdot2_f32_bf16(
-                    a, b0, acc0[p], false);
-                acc1[p] = __builtin_amdgcn_fdot2_f32_bf16(
-                    a, b1, acc1[p], false);
-            }
-        bf16_t* dst = zOut + ((c0 + c) * zstride + s * (ll)P) * VB + v0;
-        #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            bf16x2_t z2;
-            z2[0] = (__bf16)acc0[p];
-            z2[1] = (__bf16)acc1[p];
-            *(bf16x2_t*)&dst[(size_t)p * VB] = z2;
-        }
-    }
-}
-
-// raw-r variant: dot3s with the normalize deferred (bf16 Z only)
-extern "C" void launch_fcma_corr_raw(const void* At, const void* B,
-                                     void* zOut, ll E, ll L, ll VB,
-                                     ll C, ll zstride, int P,
-                                     hipStream_t stream) {
-    ll nSubj = E / P;
-    static int vpt = -1;
-    if (vpt < 0) {
-        const char* e = getenv("BRAINIAK_CORR_VPT");
-        vpt = 1;
-        if (e && atoi(e) == 2) vpt = 2;
-        if (e && atoi(e) == 3) vpt = 3;   // adjacent-pair variant
-    }
-    ll grid3 = ceil_div(C, 128) * nSubj
-             * ceil_div(VB, (ll)((vpt > 1 ? 2 : 1) * C3_VT));
-    #define RAW_CASE(TP, TL)                                             \
-        do {                                                             \
-            if (vpt == 3)                                                \
-                hipLaunchKernelGGL((k_corr_raw_pair<TP, TL, 128>),       \
-                                   dim3(grid3), dim3(256), 0, stream,    \
-                                   (const bf16_t*)At,                    \
-                                   (const bf16_t*)B, (bf16_t*)zOut, E,   \
-                                   VB, C, zstride);                      \
-            else if (vpt == 2)                                           \
-                hipLaunchKernelGGL((k_corr_raw_v2<TP, TL, 128>),         \
-                                   dim3(grid3), dim3(256), 0, stream,    \
-                                   (const bf16_t*)At,                    \
-                                   (const bf16_t*)B, (bf16_t*)zOut, E,   \
-                                   VB, C, zstride);                      \
-            else                                                         \
-                hipLaunchKernelGGL((k_corr_norm_dot3s<TP, TL, 128,       \
-                                                      bf16_t, true>),    \
-                                   dim3(grid3), dim3(256), 0, stream,    \
-                                   (const bf16_t*)At,                    \
-                                   (const bf16_t*)B, (bf16_t*)zOut, E,   \
-                                   VB, C, /*mode=*/0, zstride);          \
-        } while (0)
-    if (P == 4) {
-        switch (L) {
-            case 8:  RAW_CASE(4, 8);  return;
-            case 12: RAW_CASE(4, 12); return;
-            case 16: RAW_CASE(4, 16); return;
-            case 20: RAW_CASE(4, 20); return;
-            case 24: RAW_CASE(4, 24); return;
-            case 28: RAW_CASE(4, 28); return;
-            case 32: RAW_CASE(4, 32); return;
-            case 36: RAW_CASE(4, 36); return;
-            case 40: RAW_CASE(4, 40); return;
-        }
-    } else if (P == 2) {
-        switch (L) {
-            case 8:  RAW_CASE(2, 8);  return;
-            case 12: RAW_CASE(2, 12); return;
-            case 16: RAW_CASE(2, 16); return;
-            case 20: RAW_CASE(2, 20); return;
-            case 24: RAW_CASE(2, 24); return;
-            case 28: RAW_CASE(2, 28); return;
-            case 32: RAW_CASE(2, 32); return;
-            case 36: RAW_CASE(2, 36); return;
-            case 40: RAW_CASE(2, 40); return;
-        }
-    }
-    #undef RAW_CASE
-}
-
-static int duo_ct(void) {
-    static int ct = -1;
-    if (ct < 0) {
-        const char* e = getenv("BRAINIAK_DUO_CT");
-        ct = (e && atoi(e) == 64) ? 64 : 128;
-    }
-    return ct;
-}
-
-static ll duo_corr_blocks(ll C, ll E, int P, ll VB) {
-    ll nSubj = E / P;
-    return ceil_div(C, duo_ct()) * nSubj * ceil_div(VB, C3_VT);
-}
-
-extern "C" ll fcma_duo_gram_blocks(ll Cg, ll Eg, ll nsplit) {
-    ll eb = Eg / 64;
-    return Cg * eb * eb * nsplit;
-}
-
-extern "C" void launch_fcma_corr_gram_duo(
-    const void* At, const void* B, void* zOut, ll E, ll L, ll VB, ll C,
-    ll zstride, int P,
-    const void* Zprev, float* G, ll Cg, ll Eg, ll Vg, ll nsplit,
-    const float* GpSum, float* GSumOut, ll Cs, ll nsplitSum,
-    int do_shrink, hipStream_t stream) {
-    ll nCorr = duo_corr_blocks(C, E, P, VB);
-    ll nGram = (G != nullptr) ? fcma_duo_gram_blocks(Cg, Eg, nsplit)
-                              : 0;
-    ll nSum = (GSumOut != nullptr) ? Cs : 0;
-    ll grid = nCorr + nGram + nSum;
-    const bool dz = (Eg != 64);
-    const bool ct64 = duo_ct() == 64;
-    #define DUO_ONE(TP, TL, DZV, CTV)                                    \
-        hipLaunchKernelGGL((k_corr_gram_duo<TP, TL, TP, DZV, CTV>),      \
-                           dim3(grid), dim3(256), 0, stream,             \
-                           (const bf16_t*)At, (const bf16_t*)B,          \
-                           (bf16_t*)zOut, E, VB, C, zstride,             \
-                           (const bf16_t*)Zprev, G, Cg, Eg, Vg,          \
-                           nsplit, GpSum, GSumOut, Cs, nsplitSum,        \
-                           do_shrink, nCorr, nGram, nSum)
-    #define DUO_CASE(TP, TL)                                             \
-        do {                                                             \
-            if (dz)         DUO_ONE(TP, TL, true, 128);                  \
-            else if (ct64)  DUO_ONE(TP, TL, false, 64);                  \
-            else            DUO_ONE(TP, TL, false, 128);                 \
-        } while (0)
-    if (P == 4) {
-        switch (L) {
-            case 8:  DUO_CASE(4, 8);  return;
-            case 12: DUO_CASE(4, 12); return;
-            case 16: DUO_CASE(4, 16); return;
-            case 20: DUO_CASE(4, 20); return;
-            case 24: DUO_CASE(4, 24); return;
-            case 28: DUO_CASE(4, 28); return;
-            case 32: DUO_CASE(4, 32); return;
-            case 36: DUO_CASE(4, 36); return;
-            case 40: DUO_CASE(4, 40); return;
-        }
-    } else if (P == 2) {
-        switch (L) {
-            case 8:  DUO_CASE(2, 8);  return;
-            case 12: DUO_CASE(2, 12); return;
-            case 16: DUO_CASE(2, 16); return;
-            case 20: DUO_CASE(2, 20); return;
-            case 24: DUO_CASE(2, 24); return;
-            case 28: DUO_CASE(2, 28); return;
-            case 32: DUO_CASE(2, 32); return;
-            case 36: DUO_CASE(2, 36); return;
-            case 40: DUO_CASE(2, 40); return;
-        }
-    }
-    #undef DUO_CASE
-}
 
 extern "C" void launch_fcma_gram_fp8(const void* Z, float* G, ll C, ll E,
                                      ll V, ll nsplit,
@@ -2262,50 +1406,6 @@ extern "C" void launch_fcma_gram_fp8(const void* Z, float* G, ll C, ll E,
                        (const fp8_t*)Z, G, C, E, V, nsplit);
 }
 
-// fp8-output corr+normalize: the dot3s kernel with an e4m3 Z store.
-// P in {2, 4}, even L (the production dot3s envelope); At required.
-extern "C" int fcma_corr_norm_z8_supported(ll E, int P, ll L) {
-    return (P == 2 || P == 4) && (L % 2) == 0 && (E % P) == 0;
-}
-
-extern "C" void launch_fcma_corr_norm_z8(const void* At, const void* B,
-                                         void* zOut, ll E, ll L, ll VB,
-                                         ll C, ll zstride,
-                                         int P, hipStream_t stream) {
-    ll nSubj = E / P;
-    ll grid3 = ceil_div(C, 128) * nSubj * ceil_div(VB, C3_VT);
-    #define Z8_CASE(TP, TL)                                              \
-        hipLaunchKernelGGL((k_corr_norm_dot3s<TP, TL, 128, fp8_t>),      \
-                           dim3(grid3), dim3(256), 0, stream,            \
-                           (const bf16_t*)At, (const bf16_t*)B,          \
-                           (fp8_t*)zOut, E, VB, C, /*mode=*/0, zstride)
-    if (P == 4) {
-        switch (L) {
-            case 8:  Z8_CASE(4, 8);  return;
-            case 12: Z8_CASE(4, 12); return;
-            case 16: Z8_CASE(4, 16); return;
-            case 20: Z8_CASE(4, 20); return;
-            case 24: Z8_CASE(4, 24); return;
-            case 28: Z8_CASE(4, 28); return;
-            case 32: Z8_CASE(4, 32); return;
-            case 36: Z8_CASE(4, 36); return;
-            case 40: Z8_CASE(4, 40); return;
-        }
-    } else if (P == 2) {
-        switch (L) {
-            case 8:  Z8_CASE(2, 8);  return;
-            case 12: Z8_CASE(2, 12); return;
-            case 16: Z8_CASE(2, 16); return;
-            case 20: Z8_CASE(2, 20); return;
-            case 24: Z8_CASE(2, 24); return;
-            case 28: Z8_CASE(2, 28); return;
-            case 32: Z8_CASE(2, 32); return;
-            case 36: Z8_CASE(2, 36); return;
-            case 40: Z8_CASE(2, 40); return;
-        }
-    }
-    #undef Z8_CASE
-}
 
 extern "C" void launch_fcma_gram_f32(const float* Z, float* G, ll C, ll E,
                                      ll V, hipStream_t stream) {
