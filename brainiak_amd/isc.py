@@ -21,6 +21,15 @@ MI355X additions:
    sum rides ONE all-reduce, and each rank correlates its subjects
    against the leave-one-out mean on its own GPU (BASELINE config 4:
    50k voxels x 32 subjects over xGMI);
+ - ``isc`` itself takes ``device=``: per voxel, the correlation of every
+   subject with its leave-one-out mean, or of every subject pair, as a
+   centred two-pass fp64 correlation straight from the [TR, voxel,
+   subject] layout, in voxel chunks (``_isc_corr``: the HIP kernels
+   ``ops.isc_loo`` / ``ops.isc_pairwise`` on a GPU, a torch twin
+   elsewhere), under the NaN policy of the numpy path; the summary
+   statistic is ``_resample_stat`` with one identity draw.
+   ``timeshift_isc`` / ``phaseshift_isc`` take its result as
+   ``observed=`` and then skip their host ``isc`` call;
  - ``bootstrap_isc`` / ``permutation_isc`` / leave-one-out
    ``timeshift_isc`` take ``device=``: the null distribution is then a
    per-draw gather + median / Fisher mean over a fixed table
@@ -137,8 +146,23 @@ def _pairwise_voxel_correlations(data):
     return gram[:, iu[0], iu[1]].T
 
 
-def isc(data, pairwise=False, summary_statistic=None, tolerate_nans=True):
-    """Intersubject correlation per voxel (leave-one-out or pairwise)."""
+def isc(data, pairwise=False, summary_statistic=None, tolerate_nans=True,
+        device=None):
+    """Intersubject correlation per voxel (leave-one-out or pairwise).
+
+    ``device`` (``"cpu"``, ``"cuda"``, a ``torch.device``): compute on
+    that device (``_isc_corr``: the HIP kernels ``ops.isc_loo`` /
+    ``ops.isc_pairwise`` on a GPU, their torch twin elsewhere), in voxel
+    chunks; ``None`` keeps the numpy path.  The device path returns the
+    same shapes and type (numpy float64) under the same NaN policy.  Its
+    arithmetic is fp64 whatever the input dtype.  There ``data`` may
+    also be a 3-D ``torch.Tensor`` [TR, voxel, subject] (fp32 or fp64,
+    on any device); one that already lives on the compute device is not
+    copied through the host.
+    """
+    if device is not None:
+        return _isc_device(data, pairwise, summary_statistic,
+                           tolerate_nans, device)
     data, n_TRs, n_voxels, n_subjects = _check_timeseries_input(data)
 
     if n_subjects == 2:
@@ -493,7 +517,10 @@ def _stat_over_rows(x, stat):
         # NaNs sort last; numpy's rule for an even count is the
         # mean of the two middle values (torch.nanmedian takes
         # the lower one)
-        xs = torch.sort(x, dim=1).values
+        # (a GPU sort orders by bit pattern and puts a NaN whose sign bit
+        # is set first, and arithmetic on the GPU does produce those: all
+        # NaNs are made the positive one)
+        xs = torch.sort(torch.where(torch.isnan(x), nan, x), dim=1).values
         hi = (n // 2).clamp(max=R - 1)
         lo = ((n - 1) // 2).clamp(min=0)
         v_hi = torch.gather(xs, 1, hi[:, None, :])[:, 0, :]
@@ -832,6 +859,236 @@ def _phaseshift_null_device(data, phases, pairwise, summary_statistic,
     return distribution
 
 
+# --------------------------------------------------------------------------
+# device path of the observed ISC
+#
+# Per voxel the work is one Pearson correlation per subject (against the
+# leave-one-out mean) or per subject pair, each a centred two-pass
+# r = sxy / sqrt(sxx * syy).  ``_isc_corr`` is that step with the voxel
+# NaN policy applied: the HIP kernels ``ops.isc_loo`` / ``ops.isc_pairwise``
+# on a GPU tensor, a torch twin of the same arithmetic anywhere else.  The
+# summary statistic over the rows is ``_resample_stat`` with one identity
+# draw.  Voxels are independent, so the array streams through in chunks.
+# --------------------------------------------------------------------------
+
+# byte budget of one voxel chunk of the observed ISC
+_ISC_CHUNK_BYTES = 2 << 30
+# chunk-sized tensors alive at the twin's peak (the fp64 series, the
+# leave-one-out means, their centred forms, a product, a NaN mask)
+_ISC_CHUNK_COPIES = 6
+
+
+def _isc_min_clean(tolerate_nans, n_subjects):
+    """NaN-free subjects a voxel needs under a float ``tolerate_nans``
+    (the comparison of ``_drop_bad_voxels``); None without a threshold."""
+    if tolerate_nans is True or not isinstance(tolerate_nans, float):
+        return None
+    if not 0.0 <= tolerate_nans <= 1.0:
+        raise ValueError("If threshold to tolerate NaNs is a float, "
+                         "it must be between 0.0 and 1.0; got "
+                         f"{tolerate_nans}")
+    return n_subjects * tolerate_nans
+
+
+def _isc_corr_torch(x, pairwise, tolerant, min_clean):
+    """Torch twin of ``ops.isc_loo`` / ``ops.isc_pairwise`` on any
+    device: x fp64 [T, c, S] -> r [S or pairs, c]."""
+    import torch
+    n_TRs, _, n_subjects = x.shape
+    nan_somewhere = torch.isnan(x).any(dim=0)           # [c, S]
+    clean = (~nan_somewhere).sum(dim=1)
+    keep = clean > 0
+    if min_clean is not None:
+        keep &= clean.to(torch.float64) >= min_clean
+    if pairwise:
+        xd = x - x.mean(dim=0)
+        gram = torch.einsum("tvi,tvj->vij", xd, xd)     # [c, S, S]
+        sxx = torch.diagonal(gram, dim1=1, dim2=2)      # [c, S]
+        iu = torch.triu_indices(n_subjects, n_subjects, offset=1,
+                                device=x.device)
+        r = gram[:, iu[0], iu[1]] / torch.sqrt(sxx[:, iu[0]]
+                                               * sxx[:, iu[1]])
+    else:
+        if tolerant:
+            finite = torch.isfinite(x)
+            zero = torch.zeros((), dtype=x.dtype, device=x.device)
+            totals = torch.where(torch.isnan(x), zero, x).sum(
+                dim=2, keepdim=True)
+            counts = finite.sum(dim=2, keepdim=True)
+            loo = (totals - torch.where(finite, x, zero)) \
+                / (counts - finite.to(counts.dtype))
+        else:
+            loo = (x.sum(dim=2, keepdim=True) - x) / (n_subjects - 1)
+        xd = x - x.mean(dim=0)
+        ld = loo - loo.mean(dim=0)
+        r = (xd * ld).sum(dim=0) / torch.sqrt((xd * xd).sum(dim=0)
+                                              * (ld * ld).sum(dim=0))
+    r = r.t().contiguous()
+    r[:, ~keep] = float("nan")
+    return r
+
+
+def _isc_corr(x, v0, nv, pairwise, tolerant, min_clean):
+    """Correlations of the voxels [v0, v0 + nv) of x (fp64 [T, V, S],
+    contiguous) with the voxel NaN policy applied: rows are subjects
+    against their leave-one-out mean (the NaN-skipping one if
+    ``tolerant``), or subject pairs in ``combinations`` order.  A voxel
+    without a NaN-free subject, or with fewer than ``min_clean`` of them
+    (None: no threshold), is NaN in every row.
+
+    A GPU tensor goes through the HIP kernels ``ops.isc_loo`` /
+    ``ops.isc_pairwise`` (pairwise while S is within
+    ``ops.isc_pairwise_max_subjects()``), which read the window in
+    place; everything else, and everything under
+    ``BRAINIAK_ISC_CORR=torch``, takes the torch twin.  Returns an fp64
+    tensor [rows, nv] on x's device.
+    """
+    from . import ops
+    if (x.is_cuda
+            and os.environ.get("BRAINIAK_ISC_CORR", "") != "torch"
+            and ops.require_hip()
+            and (not pairwise
+                 or x.shape[2] <= ops.isc_pairwise_max_subjects())):
+        need = -1.0 if min_clean is None else float(min_clean)
+        if pairwise:
+            return ops.isc_pairwise(x, need, v0, nv)
+        return ops.isc_loo(x, tolerant, need, v0, nv)
+    return _isc_corr_torch(x[:, v0:v0 + nv, :], pairwise, tolerant,
+                           min_clean)
+
+
+class _PinnedStage:
+    """One pinned host buffer that the voxel chunks of a host array pass
+    through on their way to a GPU.  Gathering the strided window
+    [T, a:b, S] into it is a threaded copy and the upload from it runs
+    at the link's rate; torch's own strided host-to-device copy goes
+    through a fresh pageable temporary per chunk (measured at 50k x 32 x
+    200 in chunks of 6912 voxels: 4 + 6 ms a chunk against 80 ms)."""
+
+    def __init__(self, x, chunk, dev):
+        import torch
+        n_TRs, n_voxels, n_subjects = x.shape
+        self.dev = dev
+        self.buf = torch.empty(
+            n_TRs * min(chunk, n_voxels) * n_subjects, dtype=x.dtype,
+            pin_memory=True)
+        self.read = None                    # event: the last upload is done
+
+    def upload(self, window):
+        import torch
+        if self.read is not None:
+            self.read.synchronize()         # the buffer is free again
+        staged = self.buf[:window.numel()].view(window.shape)
+        staged.copy_(window)
+        out = staged.to(self.dev, non_blocking=True)
+        self.read = torch.cuda.Event()
+        self.read.record(torch.cuda.current_stream(self.dev))
+        return out
+
+
+def _isc_chunk_to_device(x, a, b, dev, stage=None):
+    """Voxels [a, b) of x [T, V, S] as (tensor, v0, nv) for ``_isc_corr``:
+    x itself with the window when it already is an fp64 contiguous
+    tensor on the compute device, a contiguous fp64 copy of the window
+    there otherwise (through ``stage``, a ``_PinnedStage``, if given)."""
+    import torch
+    if x.device == dev and x.dtype == torch.float64 and x.is_contiguous():
+        return x, a, b - a
+    window = x[:, a:b, :]
+    if stage is not None:
+        window = stage.upload(window)
+    xc = window.to(device=dev, dtype=torch.float64).contiguous()
+    return xc, 0, b - a
+
+
+def _isc_to_host(t):
+    return t.cpu().numpy()
+
+
+def _isc_device(data, pairwise, summary_statistic, tolerate_nans, device):
+    """``isc`` on a torch device, in voxel chunks."""
+    import torch
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(data, torch.Tensor):
+        if data.dim() != 3:
+            raise ValueError("Input tensor should have 3 dimensions "
+                             f"(got {data.dim()})!")
+        if data.dtype not in (torch.float32, torch.float64):
+            raise ValueError("Input tensor should be fp32 or fp64")
+        x = data.detach()
+    else:
+        data, _, _, _ = _check_timeseries_input(data)
+        data = np.asarray(data)
+        try:
+            x = torch.from_numpy(data)
+        except (TypeError, ValueError):     # e.g. negative strides
+            x = torch.from_numpy(np.ascontiguousarray(data,
+                                                      dtype=np.float64))
+    n_TRs, n_voxels, n_subjects = x.shape
+    if n_TRs < 1 or n_subjects < 2:
+        raise ValueError("isc: the device path needs at least 1 TR and "
+                         "2 subjects")
+    if n_subjects == 2:
+        logger.info("Only two subjects! Simply computing Pearson "
+                    "correlation.")
+        summary_statistic = None
+        pairwise = True                     # the one pair is the result
+    if summary_statistic and summary_statistic not in ('mean', 'median'):
+        raise ValueError("Summary statistic must be 'mean' or 'median'")
+    min_clean = _isc_min_clean(tolerate_nans, n_subjects)
+    tolerant = bool(tolerate_nans)
+
+    n_rows = n_subjects * (n_subjects - 1) // 2 if pairwise \
+        else n_subjects
+    per_voxel = 8 * (n_subjects * max(n_TRs, n_subjects)
+                     * _ISC_CHUNK_COPIES + 4 * n_rows)
+    chunk = max(64, _ISC_CHUNK_BYTES // per_voxel // 64 * 64)
+    iscs = np.empty((1 if summary_statistic else n_rows, n_voxels))
+    stage = None
+    if dev.type == "cuda" and x.device.type == "cpu" and n_voxels:
+        try:
+            stage = _PinnedStage(x, chunk, dev)
+        except RuntimeError:                # no pinned memory to be had
+            stage = None
+    for a in range(0, n_voxels, chunk):
+        b = min(n_voxels, a + chunk)
+        xc, v0, nv = _isc_chunk_to_device(x, a, b, dev, stage)
+        rows = _isc_corr(xc, v0, nv, pairwise, tolerant, min_clean)
+        del xc
+        if summary_statistic:
+            rows = _resample_stat(
+                rows[:, None, :], np.arange(n_rows)[None, :], None,
+                np.ones((1, n_rows), dtype=np.int8), summary_statistic)
+        iscs[:, a:b] = _isc_to_host(rows)
+        del rows
+    return iscs[0] if iscs.shape[0] == 1 else iscs
+
+
+def _expected_observed_shape(n_voxels, n_subjects, pairwise,
+                             summary_statistic):
+    """Shape of ``isc(data, pairwise, summary_statistic)``."""
+    if n_subjects == 2 or summary_statistic:
+        return (n_voxels,)
+    n_rows = n_subjects * (n_subjects - 1) // 2 if pairwise \
+        else n_subjects
+    return (n_voxels,) if n_rows == 1 else (n_rows, n_voxels)
+
+
+def _check_observed(observed, n_voxels, n_subjects, pairwise,
+                    summary_statistic):
+    """A caller's ``observed=`` as an array of the shape the internal
+    ``isc`` call would return."""
+    observed = np.asarray(observed)
+    want = _expected_observed_shape(n_voxels, n_subjects, pairwise,
+                                    summary_statistic)
+    if observed.shape != want:
+        raise ValueError(f"observed has shape {observed.shape}; "
+                         f"isc() of this data returns {want}")
+    return observed
+
+
 def bootstrap_isc(iscs, pairwise=False, summary_statistic='median',
                   n_bootstraps=1000, ci_percentile=95, side='right',
                   random_state=None, device=None):
@@ -1070,7 +1327,7 @@ def _loo_null_isc(surrogate, data, summary_statistic, tolerate_nans):
 
 def timeshift_isc(data, pairwise=False, summary_statistic='median',
                   n_shifts=1000, side='right', tolerate_nans=True,
-                  random_state=None, device=None):
+                  random_state=None, device=None, observed=None):
     """Circular time-shift null distribution for a one-sample ISC test.
 
     ``device`` (``"cpu"``, ``"cuda"``, a ``torch.device``): compute the
@@ -1081,15 +1338,26 @@ def timeshift_isc(data, pairwise=False, summary_statistic='median',
     in voxel chunks) and every draw is a lookup (``_resample_stat``).
     Leave-one-out only: the pair-lag tables of the pairwise test would
     be n_subjects^2 / 2 times the data.
+
+    The observed statistic comes from the host ``isc`` unless
+    ``observed`` is given: an array of the shape that call returns
+    (``ValueError`` otherwise), for instance the result of
+    ``isc(data, ..., device="cuda")`` with the same ``pairwise``,
+    ``summary_statistic`` and ``tolerate_nans``, which skips the host
+    ISC, most of a device call's time.
     """
     if device is not None and pairwise:
         raise ValueError("timeshift_isc: the device path is "
                          "leave-one-out only; use device=None with "
                          "pairwise=True")
     data, n_TRs, n_voxels, n_subjects = _check_timeseries_input(data)
-    observed = isc(data, pairwise=pairwise,
-                   summary_statistic=summary_statistic,
-                   tolerate_nans=tolerate_nans)
+    if observed is None:
+        observed = isc(data, pairwise=pairwise,
+                       summary_statistic=summary_statistic,
+                       tolerate_nans=tolerate_nans)
+    else:
+        observed = _check_observed(observed, n_voxels, n_subjects,
+                                   pairwise, summary_statistic)
     rng = _as_rng(random_state)
 
     if device is not None:
@@ -1117,7 +1385,7 @@ def timeshift_isc(data, pairwise=False, summary_statistic='median',
 
 def phaseshift_isc(data, pairwise=False, summary_statistic='median',
                    n_shifts=1000, side='right', tolerate_nans=True,
-                   random_state=None, device=None):
+                   random_state=None, device=None, observed=None):
     """FFT phase-randomization null distribution for an ISC test.
 
     ``device`` (``"cpu"``, ``"cuda"``, a ``torch.device``): compute the
@@ -1128,7 +1396,11 @@ def phaseshift_isc(data, pairwise=False, summary_statistic='median',
     once (in voxel chunks) and every draw is a dot product with that
     table (``_phase_stat``), without a per-draw FFT.  Both leave-one-out
     and ``pairwise=True`` are supported; the observed statistic still
-    comes from ``isc``.
+    comes from the host ``isc`` unless ``observed`` is given: an array
+    of the shape that call returns (``ValueError`` otherwise), for
+    instance the result of ``isc(data, ..., device="cuda")`` with the
+    same ``pairwise``, ``summary_statistic`` and ``tolerate_nans``,
+    which skips the host ISC, most of a device call's time.
 
     On the device path ``tolerate_nans`` acts as on the numpy path: with
     ``pairwise=True`` the voxels that its threshold drops are NaN in the
@@ -1140,9 +1412,13 @@ def phaseshift_isc(data, pairwise=False, summary_statistic='median',
     leaves in the surrogate.
     """
     data, n_TRs, n_voxels, n_subjects = _check_timeseries_input(data)
-    observed = isc(data, pairwise=pairwise,
-                   summary_statistic=summary_statistic,
-                   tolerate_nans=tolerate_nans)
+    if observed is None:
+        observed = isc(data, pairwise=pairwise,
+                       summary_statistic=summary_statistic,
+                       tolerate_nans=tolerate_nans)
+    else:
+        observed = _check_observed(observed, n_voxels, n_subjects,
+                                   pairwise, summary_statistic)
     rng = _as_rng(random_state)
 
     if device is not None:

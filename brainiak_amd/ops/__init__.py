@@ -25,6 +25,9 @@ factoranalysis/tfa_extension.cpp, eventseg/_utils.pyx):
                           block with a fixed spectral table + the same
                           median / Fisher mean: the null distribution of
                           the ISC phase-randomisation test
+ - ``isc_loo`` / ``isc_pairwise`` — the observed ISC itself: per-voxel
+                          leave-one-out and pairwise correlations from
+                          the [T, V, S] layout, NaN policy included
  - ``searchlight_gram`` — per-centre [E,E] Gram of a searchlight's
                           activity vectors (gather + exact-fp32 MFMA
                           syrk), the front end of the activity-based
@@ -56,6 +59,9 @@ __all__ = [
     "hmm_forward_backward",
     "hmm_viterbi",
     "hmm_viterbi_tile",
+    "isc_loo",
+    "isc_pairwise",
+    "isc_pairwise_max_subjects",
     "isc_phase_max_rows",
     "isc_phase_stat",
     "isc_resample_max_rows",
@@ -440,6 +446,54 @@ def isc_phase_max_rows() -> int:
     """Largest R the 'median' path of ``isc_phase_stat`` takes (its
     per-lane sorted columns live in LDS)."""
     return int(_ext().isc_phase_max_rows())
+
+
+# ---------------------------------------------------------------------------
+# observed ISC
+# ---------------------------------------------------------------------------
+
+def isc_loo(data: torch.Tensor, tolerant: bool, min_clean: float = -1.0,
+            v0: int = 0, nv: int = -1) -> torch.Tensor:
+    """Leave-one-out ISC of every voxel of a window of the data, from the
+    caller's layout (no transposed copy): ``k_isc_totals`` (sums over
+    the subjects), ``k_isc_loo`` (one thread per voxel and subject, a
+    centred two-pass correlation) and ``k_isc_drop`` (the voxel policy).
+
+    data fp64 [T, V, S] contiguous on the GPU, T >= 1, S >= 2.  The
+    window is the voxels [v0, v0 + nv) (``nv = -1``: up to V); it is
+    addressed in place.  ``tolerant``: the leave-one-out mean skips
+    NaNs (``np.nanmean``) instead of propagating them.  A voxel whose
+    subjects all have a NaN somewhere, or that has fewer than
+    ``min_clean`` NaN-free subjects (``min_clean < 0``: no threshold),
+    is NaN in every row.
+
+    Returns r [S, nv] fp64: r[s, v] is the correlation of subject s with
+    the mean of the others.
+    """
+    return _ext().isc_loo(data, bool(tolerant), float(min_clean), int(v0),
+                          int(nv))
+
+
+def isc_pairwise(data: torch.Tensor, min_clean: float = -1.0, v0: int = 0,
+                 nv: int = -1) -> torch.Tensor:
+    """Pairwise ISC of every voxel of a window of the data
+    (``k_isc_pairwise``: a block stages time slabs of a few voxels in
+    LDS, a thread holds a 4 x 4 tile of a voxel's centred Gram; then
+    ``k_isc_drop``).
+
+    data, the window and ``min_clean`` as in ``isc_loo``;
+    S <= ``isc_pairwise_max_subjects()``.
+
+    Returns r [S (S - 1) / 2, nv] fp64, pairs in ``combinations`` order
+    (row-major upper triangle).
+    """
+    return _ext().isc_pairwise(data, float(min_clean), int(v0), int(nv))
+
+
+def isc_pairwise_max_subjects() -> int:
+    """Largest S ``isc_pairwise`` takes (a voxel's Gram tiles fill one
+    block)."""
+    return int(_ext().isc_pairwise_max_subjects())
 
 
 # ---------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // Torch bindings for the brainiak_amd HIP/CDNA4 kernels (gfx950).
 //
 // The device code lives in fcma_kernels.hip / procrustes.hip /
-// tfa_kernels.hip / hmm_kernels.hip / isc_stats_kernels.hip (hand-written
+// tfa_kernels.hip / hmm_kernels.hip / isc_stats_kernels.hip /
+// isc_corr_kernels.hip (hand-written
 // HIP, MFMA/LDS — no library GEMMs on the FCMA path); this file validates
 // tensors, allocates outputs, and calls the extern "C" launchers on the
 // current stream.
@@ -59,6 +60,13 @@ void launch_isc_phase_stat(const double*, const double*, double*, ll, ll,
                            int, int, int, void*);
 int isc_phase_max_rows(void);
 ll isc_phase_blocks(ll, ll, int, int);
+void launch_isc_loo(const double*, double*, int*, double*, unsigned char*,
+                    ll, ll, ll, int, int, double, void*);
+ll isc_loo_blocks(ll, ll, int);
+void launch_isc_pairwise(const double*, double*, unsigned char*, ll, ll, ll,
+                         int, double, void*);
+ll isc_pairwise_blocks(ll, int);
+int isc_pairwise_max_subjects(void);
 void launch_sl_gram(const float*, const unsigned char*,
                     const unsigned char*, const ll*, float*, ll, int, int,
                     int, int, void*);
@@ -908,6 +916,61 @@ torch::Tensor isc_phase_stat(torch::Tensor table, torch::Tensor coef,
     return out;
 }
 
+// shared argument checks of the observed-ISC kernels: data fp64 [T,V,S]
+// contiguous on the GPU, the voxel window [v0, v0 + nv) inside it
+static void check_isc_corr_args(const torch::Tensor& data, ll v0, ll nv) {
+    check_3d(data, torch::kFloat64, "data");
+    ll T = data.size(0), V = data.size(1), S = data.size(2);
+    TORCH_CHECK(T >= 1, "data needs at least one time point");
+    TORCH_CHECK(S >= 2, "data needs at least two subjects (got ", S, ")");
+    TORCH_CHECK(S <= (ll)INT_MAX / 4, "too many subjects");
+    TORCH_CHECK(v0 >= 0 && nv >= 0 && v0 <= V && nv <= V - v0,
+                "voxel window [", v0, ", ", v0 + nv, ") outside [0, ", V,
+                ")");
+}
+
+torch::Tensor isc_loo(torch::Tensor data, bool tolerant, double min_clean,
+                      ll v0, ll nv) {
+    // leave-one-out ISC of the voxel window -> r [S, nv]
+    // (isc_corr_kernels.hip::k_isc_totals, k_isc_loo, k_isc_drop)
+    if (nv < 0) nv = data.dim() == 3 ? data.size(1) - v0 : 0;
+    check_isc_corr_args(data, v0, nv);
+    ll T = data.size(0), V = data.size(1), S = data.size(2);
+    auto r = torch::empty({S, nv}, data.options());
+    if (nv == 0) return r;
+    TORCH_CHECK(isc_loo_blocks(T, nv, (int)S) <= (ll)INT_MAX,
+                "too many blocks for one launch");
+    auto tot = torch::empty({T, nv}, data.options());
+    auto cnt = torch::empty({tolerant ? T : 0, nv},
+                            data.options().dtype(torch::kInt32));
+    auto flags = torch::empty({nv, S}, data.options().dtype(torch::kUInt8));
+    launch_isc_loo(data.data_ptr<double>() + v0 * S, tot.data_ptr<double>(),
+                   tolerant ? cnt.data_ptr<int>() : nullptr,
+                   r.data_ptr<double>(), flags.data_ptr<uint8_t>(), V * S, T,
+                   nv, (int)S, tolerant ? 1 : 0, min_clean, cur_stream());
+    return r;
+}
+
+torch::Tensor isc_pairwise(torch::Tensor data, double min_clean, ll v0,
+                           ll nv) {
+    // pairwise ISC of the voxel window -> r [S (S - 1) / 2, nv], pairs in
+    // combinations order (isc_corr_kernels.hip::k_isc_pairwise, k_isc_drop)
+    if (nv < 0) nv = data.dim() == 3 ? data.size(1) - v0 : 0;
+    check_isc_corr_args(data, v0, nv);
+    ll T = data.size(0), V = data.size(1), S = data.size(2);
+    TORCH_CHECK(S <= isc_pairwise_max_subjects(), "isc_pairwise needs S <= ",
+                isc_pairwise_max_subjects(), " subjects (got ", S, ")");
+    auto r = torch::empty({S * (S - 1) / 2, nv}, data.options());
+    if (nv == 0) return r;
+    TORCH_CHECK(isc_pairwise_blocks(nv, (int)S) <= (ll)INT_MAX,
+                "too many blocks for one launch");
+    auto flags = torch::empty({nv, S}, data.options().dtype(torch::kUInt8));
+    launch_isc_pairwise(data.data_ptr<double>() + v0 * S,
+                        r.data_ptr<double>(), flags.data_ptr<uint8_t>(),
+                        V * S, T, nv, (int)S, min_clean, cur_stream());
+    return r;
+}
+
 torch::Tensor searchlight_gram(torch::Tensor x, torch::Tensor mask,
                                torch::Tensor shape, torch::Tensor centres) {
     // per-centre Gram of the searchlight's activity vectors
@@ -961,6 +1024,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("centres"));
     m.def("searchlight_gram_max_e", []() { return sl_gram_max_e(); },
           "epoch cap of k_sl_gram");
+    m.def("isc_loo", &isc_loo,
+          "leave-one-out ISC of data [T,V,S] fp64 -> r [S,nv] fp64",
+          pybind11::arg("data"), pybind11::arg("tolerant"),
+          pybind11::arg("min_clean") = -1.0, pybind11::arg("v0") = 0,
+          pybind11::arg("nv") = -1);
+    m.def("isc_pairwise", &isc_pairwise,
+          "pairwise ISC of data [T,V,S] fp64 -> r [S(S-1)/2,nv] fp64",
+          pybind11::arg("data"), pybind11::arg("min_clean") = -1.0,
+          pybind11::arg("v0") = 0, pybind11::arg("nv") = -1);
+    m.def("isc_pairwise_max_subjects",
+          []() { return isc_pairwise_max_subjects(); },
+          "subject cap of k_isc_pairwise");
     m.def("isc_phase_stat", &isc_phase_stat,
           "coef [I,R,K] x table [R,K,V] + nanmedian / Fisher mean over R "
           "-> out [I,V] fp64",

@@ -30,6 +30,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "tfa_kernels.hip"),
         os.path.join(HIP_DIR, "hmm_kernels.hip"),
         os.path.join(HIP_DIR, "isc_stats_kernels.hip"),
+        os.path.join(HIP_DIR, "isc_corr_kernels.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3"],
