@@ -354,8 +354,10 @@ class CorrelationPipeline:
         the per-chunk views of its result go to the consumer in chunk
         order on the current stream.
         BRAINIAK_FCMA_SCHED=phased (or ahead) picks the kernel's
-        schedule; the results do not depend on it."""
+        schedule, BRAINIAK_FCMA_FISHER=log (or table) where its Fisher z
+        comes from; the results depend on neither."""
         sched = os.environ.get("BRAINIAK_FCMA_SCHED", "") or "auto"
+        fisher = os.environ.get("BRAINIAK_FCMA_FISHER", "") or "auto"
         a_t, b_t = self._fused_operands()
         E = self.num_epochs
         P = self.epochs_per_subj
@@ -378,7 +380,7 @@ class CorrelationPipeline:
             nsplit = max(1, min((wave // cb) // blocks, windows))
             g = ops.fcma_corr_gram_fused(a_t, b_t, start, total, P,
                                          nsplit=nsplit, shrink=shrink,
-                                         schedule=sched)
+                                         schedule=sched, fisher=fisher)
             k0 = 0
             for s_k, c_k in chunks[i:j]:
                 gk = g[k0:k0 + c_k]

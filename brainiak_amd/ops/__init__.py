@@ -210,7 +210,8 @@ def fcma_corr_gram_fused(At_all: torch.Tensor, B_t: torch.Tensor,
                          start: int, count: int, epochs_per_subj: int,
                          nsplit: int = 1, shrink: bool = True,
                          clamp: str = "auto",
-                         schedule: str = "auto") -> torch.Tensor:
+                         schedule: str = "auto",
+                         fisher: str = "auto") -> torch.Tensor:
     """Correlation + normalize + Gram in one kernel over the operands of
     ``fcma_fused_operand``: [count, 64, 64] fp32 Grams of selected voxels
     [start, start+count) of At_all against every column of B_t, with the
@@ -227,11 +228,25 @@ def fcma_corr_gram_fused(At_all: torch.Tensor, B_t: torch.Tensor,
     the kernel was first shipped with; ``"auto"`` (the default) is
     ``"ahead"``.  Epoch lengths above 32 have no ``"ahead"`` form
     (``fcma_corr_gram_fused_ahead``) and run phased whatever is asked.
-    All give the same bits."""
+    All give the same bits.
+
+    ``fisher="table"`` takes the Fisher z of a bf16-rounded correlation
+    from a table that every workgroup builds in LDS with the log path's
+    own arithmetic; ``"log"`` computes it with ``v_log_f32``; ``"auto"``
+    (the default) is the table where the instance has one
+    (``fcma_corr_gram_fused_table``: epoch lengths up to 32) and
+    ``clamp`` is ``"auto"``, the logs elsewhere.  ``"table"`` where there
+    is none is an error.  Both give the same bits."""
     return _ext().fcma_corr_gram_fused(At_all, B_t, int(start), int(count),
                                        int(epochs_per_subj), int(nsplit),
                                        bool(shrink), str(clamp),
-                                       str(schedule))
+                                       str(schedule), str(fisher))
+
+
+def fcma_corr_gram_fused_table(P: int, L: int) -> bool:
+    """True when the ``fcma_corr_gram_fused`` instance for P epochs per
+    subject and epoch length L has a Fisher-z table."""
+    return bool(_ext().fcma_corr_gram_fused_table(int(P), int(L)))
 
 
 def fcma_corr_gram_fused_ahead(P: int, L: int) -> bool:

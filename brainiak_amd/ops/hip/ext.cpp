@@ -41,9 +41,13 @@ int fcma_corr_gram_fused_lp(ll);
 int fcma_corr_gram_fused_cb(void);
 int fcma_corr_gram_fused_vt(void);
 int fcma_corr_gram_fused_ahead(int, ll);
+int fcma_corr_gram_fused_table(int, ll);
 void launch_fcma_corr_gram_fused(const void*, const void*, float*, int, ll,
-                                 ll, ll, ll, int, int, int, int, int,
+                                 ll, ll, ll, int, int, int, int, int, int,
                                  void*);
+int fcma_fisher_table_entries(void);
+void launch_fcma_fisher_table_probe(const float*, ll, float*, float*,
+                                    float*, void*);
 void launch_hmm_fb(const double*, const double*, const double*,
                    const double*, const double*, const int*, const int*,
                    double*, double*, ll, int, int, void*);
@@ -417,13 +421,19 @@ torch::Tensor fcma_fused_gram(torch::Tensor A, torch::Tensor B,
 // the task itself (the order the kernel was first shipped with); "auto"
 // is "ahead".  The LP = 64 instances have no "ahead" form and run phased
 // either way.  All give the same bits.
+// fisher = "table" takes the Fisher z of the unclamped normalize from a
+// table of the bf16 magnitudes that every workgroup builds in LDS,
+// "log" computes it (v_log_f32); "auto" is the table where the instance
+// has one (fcma_corr_gram_fused_table) and clamp is "auto".  Asking for
+// the table where there is none is an error.  Both give the same bits.
 // partials = true returns the [nsplit, count, 64, 64] slabs as the kernel
 // wrote them (unshrunk, not summed); a split without a column window
 // is an all-zero slab.
 static torch::Tensor fcma_corr_gram_fused_impl(
     torch::Tensor At_all, torch::Tensor B_t, int64_t start, int64_t count,
     int64_t P, int64_t nsplit, bool shrink, const std::string& clamp,
-    const std::string& schedule, bool partials) {
+    const std::string& schedule, const std::string& fisher,
+    bool partials) {
     check_3d(At_all, torch::kBFloat16, "At_all");
     check_3d(B_t, torch::kBFloat16, "B_t");
     ll VA = At_all.size(1), VB = B_t.size(1), LP = At_all.size(2);
@@ -462,13 +472,23 @@ static torch::Tensor fcma_corr_gram_fused_impl(
     // FS_SCHED_* of fcma_fused_kernels.hip
     const int sched = schedule == "auto" ? 0
         : (schedule == "ahead" ? 1 : 2);
+    TORCH_CHECK(fisher == "auto" || fisher == "table" || fisher == "log",
+                "fisher must be \"auto\", \"table\" or \"log\"");
+    // FS_FISHER_* of fcma_fused_kernels.hip
+    const int fish = fisher == "auto" ? 0 : (fisher == "table" ? 1 : 2);
+    if (fish == 1) {
+        TORCH_CHECK(!force_clamp, "fisher=\"table\" needs clamp=\"auto\": "
+                    "the clamp=\"always\" instances keep the logs");
+        TORCH_CHECK(fcma_corr_gram_fused_table((int)P, LP), kNoKernel,
+                    "fused table instance for row length ", LP);
+    }
     auto opts = At_all.options().dtype(torch::kFloat32);
     if (partials) {
         auto Gp = torch::empty({nsplit, count, 64, 64}, opts);
         launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
                                     Gp.data_ptr<float>(), (int)LP, VA, VB,
                                     start, count, (int)P, (int)nsplit, 0,
-                                    force_clamp, sched, cur_stream());
+                                    force_clamp, sched, fish, cur_stream());
         return Gp;
     }
     auto G = torch::empty({count, 64, 64}, opts);
@@ -477,14 +497,14 @@ static torch::Tensor fcma_corr_gram_fused_impl(
                                     G.data_ptr<float>(), (int)LP, VA, VB,
                                     start, count, (int)P, 1,
                                     shrink ? 1 : 0, force_clamp, sched,
-                                    cur_stream());
+                                    fish, cur_stream());
         return G;
     }
     auto Gp = torch::empty({nsplit, count, 64, 64}, opts);
     launch_fcma_corr_gram_fused(At_all.data_ptr(), B_t.data_ptr(),
                                 Gp.data_ptr<float>(), (int)LP, VA, VB,
                                 start, count, (int)P, (int)nsplit, 0,
-                                force_clamp, sched, cur_stream());
+                                force_clamp, sched, fish, cur_stream());
     launch_fcma_gsum(Gp.data_ptr<float>(), G.data_ptr<float>(), count,
                      64 * 64, nsplit, shrink ? 1 : 0, cur_stream());
     return G;
@@ -494,17 +514,35 @@ torch::Tensor fcma_corr_gram_fused(torch::Tensor At_all, torch::Tensor B_t,
                                    int64_t start, int64_t count, int64_t P,
                                    int64_t nsplit, bool shrink,
                                    const std::string& clamp,
-                                   const std::string& schedule) {
+                                   const std::string& schedule,
+                                   const std::string& fisher) {
     return fcma_corr_gram_fused_impl(At_all, B_t, start, count, P, nsplit,
-                                     shrink, clamp, schedule, false);
+                                     shrink, clamp, schedule, fisher, false);
 }
 
 torch::Tensor fcma_corr_gram_fused_partials(
     torch::Tensor At_all, torch::Tensor B_t, int64_t start, int64_t count,
     int64_t P, int64_t nsplit, const std::string& clamp,
-    const std::string& schedule) {
+    const std::string& schedule, const std::string& fisher) {
     return fcma_corr_gram_fused_impl(At_all, B_t, start, count, P, nsplit,
-                                     false, clamp, schedule, true);
+                                     false, clamp, schedule, fisher, true);
+}
+
+// Tests only.  r: fp32 values (bf16 patterns widened).  Returns the table
+// as a workgroup builds it, the z of the log path and the z of the
+// lookup for every r ([2, n]: r in the low and in the high half of a
+// bf16 pair), from the device functions the fused kernel runs.
+std::vector<torch::Tensor> fcma_fisher_table_probe(torch::Tensor r) {
+    TORCH_CHECK(r.is_cuda() && r.dtype() == torch::kFloat32 && r.dim() == 1
+                && r.is_contiguous(), "r: contiguous 1-D fp32 on the device");
+    auto tab = torch::empty({fcma_fisher_table_entries()}, r.options());
+    auto zlog = torch::empty_like(r);
+    auto ztab = torch::empty({2, r.numel()}, r.options());
+    launch_fcma_fisher_table_probe(r.data_ptr<float>(), r.numel(),
+                                   tab.data_ptr<float>(),
+                                   zlog.data_ptr<float>(),
+                                   ztab.data_ptr<float>(), cur_stream());
+    return {tab, zlog, ztab};
 }
 
 bool fcma_fused_gram_native(int64_t E, int64_t P, int64_t L) {
@@ -1122,13 +1160,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("At_all"), py::arg("B_t"), py::arg("start"),
           py::arg("count"), py::arg("P"), py::arg("nsplit") = 1,
           py::arg("shrink") = true, py::arg("clamp") = "auto",
-          py::arg("schedule") = "auto");
+          py::arg("schedule") = "auto", py::arg("fisher") = "auto");
     m.def("fcma_corr_gram_fused_partials", &fcma_corr_gram_fused_partials,
           "the [nsplit, count, 64, 64] slabs of fcma_corr_gram_fused as "
           "the kernel writes them (unshrunk, not summed)",
           py::arg("At_all"), py::arg("B_t"), py::arg("start"),
           py::arg("count"), py::arg("P"), py::arg("nsplit"),
-          py::arg("clamp") = "auto", py::arg("schedule") = "auto");
+          py::arg("clamp") = "auto", py::arg("schedule") = "auto",
+          py::arg("fisher") = "auto");
+    m.def("fcma_corr_gram_fused_table",
+          [](int64_t P, int64_t L) {
+              return fcma_corr_gram_fused_table((int)P, L) != 0;
+          }, "whether the (P, L) instance takes the Fisher z from the LDS "
+          "table (clamp \"auto\")");
+    m.def("fcma_fisher_table_probe", &fcma_fisher_table_probe,
+          "tests only: (table, log-path z, lookup z) for fp32 values r");
     m.def("fcma_corr_gram_fused_ahead",
           [](int64_t P, int64_t L) {
               return fcma_corr_gram_fused_ahead((int)P, L) != 0;

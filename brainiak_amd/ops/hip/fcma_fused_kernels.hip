@@ -44,7 +44,12 @@
 //           find that; the wave then normalizes the same correlations
 //           again, clamped, before it stores.  The FORCE instances
 //           (force_clamp) run the clamped normalize for every task and
-//           test nothing.  Both give the same bits.
+//           test nothing.  Both give the same bits.  The TABLE
+//           instances (LP <= 32, the default there) read the Fisher z
+//           of the unclamped normalize from an LDS table of the bf16
+//           magnitudes instead of computing four logs per pair
+//           (fisher_z_table below); an |r| >= 1 reads a NaN entry, so
+//           the NaN variance and the clamped redo stay as they are.
 //  phase 3  wave w owns voxels 2w, 2w+1: four 16-row bands as bf16x8
 //           fragments, the 10 upper-triangle 16x16x32 MFMAs per voxel;
 //           accumulators (40 fp32 / voxel / lane) persist across the
@@ -145,19 +150,72 @@ __device__ __forceinline__ f32x4 corr_mfma(const FragT<LP>& a,
 //   sq   = fma(z[P-1], z[P-1], ... fma(z0, z0, z1 * z1))
 //   var  = fma(sq, 1/P, -(mean * mean)),  mean = sum * (1/P)
 //   out  = fma(-sum, 1/P, z) * inv        (= (z - mean) * inv exactly)
-// sum starts from z[0], not 0 + z[0]: z is never -0 (log2(1) is +0 and
-// x - x is +0), so the add changed nothing.
+// sum starts from z[0], not 0 + z[0]: a z from the logs is never -0
+// (log2(1) is +0 and x - x is +0), so the add changed nothing.  (A z
+// from the table can be -0; fisher_z_table says why no Gram sees it.)
 //
 // Returns the wave's lanes in which the unclamped form met a 1 +- r <= 0
 // (CLAMP = false; always 0 for CLAMP = true).  There, and only there,
 // some z is +-inf or NaN, so sq is +inf or NaN and var is NaN; for
 // |r| < 1 everything is finite.  v_cmp_u_f32 takes two operands, so the
 // four variances of a lane cost two compares, OR-ed on the scalar unit.
+// z of one column pair: log2(1 + r) - log2(1 - r), the Fisher z up to
+// the factor the z-score cancels
+template <bool CLAMP>
+__device__ __forceinline__ f32x2 fisher_z_log(f32x2 r2) {
+    #pragma clang fp contract(off)
+    f32x2 num = 1.0f + r2;
+    f32x2 den = 1.0f - r2;
+    if constexpr (CLAMP) {
+        num[0] = __builtin_fmaxf(num[0], 1e-4f);
+        num[1] = __builtin_fmaxf(num[1], 1e-4f);
+        den[0] = __builtin_fmaxf(den[0], 1e-4f);
+        den[1] = __builtin_fmaxf(den[1], 1e-4f);
+    }
+    const f32x2 ln = {__builtin_amdgcn_logf(num[0]),
+                      __builtin_amdgcn_logf(num[1])};
+    const f32x2 ld = {__builtin_amdgcn_logf(den[0]),
+                      __builtin_amdgcn_logf(den[1])};
+    return ln - ld;
+}
+
+// within-subject z-score of one column pair (half h of the lane's four
+// columns) from its P Fisher z; CHECK adds the NaN-variance test
+template <int P, bool CHECK>
+__device__ __forceinline__ unsigned long long normalize_half(
+    const f32x2 (&z)[P], int h, nbf16x4 (&zo)[P]) {
+    #pragma clang fp contract(off)
+    const f32x2 rP = (f32x2)(1.0f / (float)P);
+    unsigned long long missed = 0;
+    f32x2 sum = z[0];
+    f32x2 sq = __builtin_elementwise_fma(z[0], z[0], z[1] * z[1]);
+    sum += z[1];
+    #pragma unroll
+    for (int p = 2; p < P; ++p) {
+        sum += z[p];
+        sq = __builtin_elementwise_fma(z[p], z[p], sq);
+    }
+    const f32x2 mean = sum * rP;
+    const f32x2 var = __builtin_elementwise_fma(sq, rP, -(mean * mean));
+    if constexpr (CHECK)
+        missed = __builtin_amdgcn_ballot_w64(
+            __builtin_isunordered(var[0], var[1]));
+    f32x2 inv;
+    #pragma unroll
+    for (int j = 0; j < 2; ++j)
+        inv[j] = (var[j] <= 0.f) ? 0.f : __builtin_amdgcn_rsqf(var[j]);
+    #pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const f32x2 o = __builtin_elementwise_fma(-sum, rP, z[p]) * inv;
+        zo[p][2 * h] = (__bf16)o[0];
+        zo[p][2 * h + 1] = (__bf16)o[1];
+    }
+    return missed;
+}
+
 template <int P, bool CLAMP>
 __device__ __forceinline__ unsigned long long normalize_task(
     const f32x4 (&rq)[P], nbf16x4 (&zo)[P]) {
-    #pragma clang fp contract(off)
-    const f32x2 rP = (f32x2)(1.0f / (float)P);
     unsigned long long missed = 0;
     #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -165,43 +223,114 @@ __device__ __forceinline__ unsigned long long normalize_task(
         #pragma unroll
         for (int p = 0; p < P; ++p) {
             const f32x2 r2 = {rq[p][2 * h], rq[p][2 * h + 1]};
-            f32x2 num = 1.0f + r2;
-            f32x2 den = 1.0f - r2;
-            if constexpr (CLAMP) {
-                num[0] = __builtin_fmaxf(num[0], 1e-4f);
-                num[1] = __builtin_fmaxf(num[1], 1e-4f);
-                den[0] = __builtin_fmaxf(den[0], 1e-4f);
-                den[1] = __builtin_fmaxf(den[1], 1e-4f);
-            }
-            const f32x2 ln = {__builtin_amdgcn_logf(num[0]),
-                              __builtin_amdgcn_logf(num[1])};
-            const f32x2 ld = {__builtin_amdgcn_logf(den[0]),
-                              __builtin_amdgcn_logf(den[1])};
-            z[p] = ln - ld;
+            z[p] = fisher_z_log<CLAMP>(r2);
         }
-        f32x2 sum = z[0];
-        f32x2 sq = __builtin_elementwise_fma(z[0], z[0], z[1] * z[1]);
-        sum += z[1];
-        #pragma unroll
-        for (int p = 2; p < P; ++p) {
-            sum += z[p];
-            sq = __builtin_elementwise_fma(z[p], z[p], sq);
-        }
-        const f32x2 mean = sum * rP;
-        const f32x2 var = __builtin_elementwise_fma(sq, rP, -(mean * mean));
-        if constexpr (!CLAMP)
-            missed |= __builtin_amdgcn_ballot_w64(
-                __builtin_isunordered(var[0], var[1]));
-        f32x2 inv;
-        #pragma unroll
-        for (int j = 0; j < 2; ++j)
-            inv[j] = (var[j] <= 0.f) ? 0.f : __builtin_amdgcn_rsqf(var[j]);
+        missed |= normalize_half<P, !CLAMP>(z, h, zo);
+    }
+    return missed;
+}
+
+// The Fisher z from a table.  Its argument has just been rounded to
+// bf16, so z is a function of a 16-bit pattern.  It is exactly odd
+// (ld - ln == -(ln - ld)), exactly +0 for |r| <= 2^-25 = 0x3300 (both
+// 1 + r and 1 - r round to 1), and needs the clamp exactly for |r| >= 1
+// = 0x3F80.  What is left are the magnitudes 0x3301 .. 0x3F7F:
+//   entry 0            +0
+//   entry i            fisher_z_log<false> of the magnitude 0x3300 + i
+//   entry FS_TAB_LAST  a quiet NaN, for |r| >= 1, infinities and NaNs
+// Every workgroup builds the table in LDS at kernel start with the very
+// function the log path runs, so it holds that path's bits by
+// construction.  The table lies at the start of the kernel's one LDS
+// array: the index scaled to bytes is the ds_read address.
+#define FS_TAB_LO 0x3300                       // 2^-25
+#define FS_TAB_LAST (0x3F80 - FS_TAB_LO)       // 3200
+#define FS_TAB_BYTES ((FS_TAB_LAST + 1) * 4 + 12)   // 16-byte multiple
+
+__device__ __forceinline__ void fisher_table_build(float* tab, int tid,
+                                                   int nthreads) {
+    for (int i = tid; i <= FS_TAB_LAST; i += nthreads) {
+        const float r = __builtin_bit_cast(
+            float, (unsigned)(FS_TAB_LO + i) << 16);
+        float z = fisher_z_log<false>((f32x2){r, r})[0];
+        if (i == 0) z = 0.f;
+        if (i == FS_TAB_LAST) z = __builtin_nanf("");
+        tab[i] = z;
+    }
+}
+
+// Byte offsets into the table of the two correlations a, b:
+//   4 * min(sat_sub(|bf16(r)| as bits, FS_TAB_LO), FS_TAB_LAST)
+// on the packed pair that comes out of the convert.  The sign bit goes
+// with a packed shift by one, which leaves twice the magnitude, so the
+// subtraction and the minimum run on doubled values; the second factor
+// of two comes with the split into two addresses: v_mad_u32_u16 takes
+// the low half times two, a shift by 15 the high half (twice the index
+// is below 2^15, so nothing of the low half gets into it).  Eight
+// instructions per pair with the two v_bfi_b32 of the sign.
+// The compiler has no pattern for that multiply-add (it emits a mask
+// and a shift, and that build measured 2.0 ms per pass slower), hence
+// the asm; its source is the v_pk_min_u16 above.  The convert would
+// take |x| source modifiers as well, but only through inline asm, and
+// the compiler keeps no MFMA-to-VALU distance for a register that
+// inline asm reads: the phased instances, whose correlations come
+// straight out of the MFMAs, read stale registers that way and fail the
+// bit tests.  No inline asm may read a correlation.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void fisher_table_offsets(float a, float b,
+                                                     unsigned& lo,
+                                                     unsigned& hi) {
+    const f32x2 r2 = {a, b};
+    const unsigned u = __builtin_bit_cast(
+        unsigned, __builtin_convertvector(r2, nbf16x2));
+    u16x2 i = __builtin_bit_cast(u16x2, u) << (u16x2)(unsigned short)1;
+    i = __builtin_elementwise_sub_sat(
+        i, (u16x2)(unsigned short)(2 * FS_TAB_LO));
+    i = __builtin_elementwise_min(i,
+                                  (u16x2)(unsigned short)(2 * FS_TAB_LAST));
+    const unsigned x = __builtin_bit_cast(unsigned, i);
+    // x must stay the result of a VALU instruction the compiler sees
+    // (here the v_pk_min_u16), never an MFMA result: asm operands get no
+    // MFMA wait states
+    asm("v_mad_u32_u16 %0, %1, 2, 0" : "=v"(lo) : "v"(x));
+    hi = x >> 15;
+}
+
+// z of one column pair of unrounded correlations.  The magnitude comes
+// from the table, the sign from r itself (bf16 rounding keeps it).  A
+// negative r with |r| <= 2^-25 therefore gives -0 where the log path
+// gives +0 (log2(1) - log2(1)).  That zero stays: it can flip the sign
+// of a zero in the z image and nothing else.  In the z-score a -0 adds
+// like +0 to anything non-zero, var = fma(sq, 1/P, -(mean * mean)) is
+// +0 + -0 = +0 either way, and the output is a zero of either sign.  In
+// the Gram every product with it is a zero, the accumulators start at
+// +0, and +0 plus a zero of either sign is +0 while anything else plus a
+// zero is itself: no Gram bit depends on the sign.
+__device__ __forceinline__ f32x2 fisher_z_table(f32x2 r2,
+                                                const unsigned char* tab) {
+    unsigned lo, hi;
+    fisher_table_offsets(r2[0], r2[1], lo, hi);
+    const float m0 = *(const float*)(tab + lo);
+    const float m1 = *(const float*)(tab + hi);
+    return (f32x2){__builtin_copysignf(m0, r2[0]),
+                   __builtin_copysignf(m1, r2[1])};
+}
+
+// normalize_task<P, false> with the z from the table.  A task that holds
+// an |r| >= 1 (or a non-finite r) reads the NaN entry, its variance is
+// NaN, and the lanes come back as with the unclamped logs.
+template <int P>
+__device__ __forceinline__ unsigned long long normalize_task_table(
+    const f32x4 (&r)[P], const unsigned char* tab, nbf16x4 (&zo)[P]) {
+    unsigned long long missed = 0;
+    #pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        f32x2 z[P];
         #pragma unroll
         for (int p = 0; p < P; ++p) {
-            const f32x2 o = __builtin_elementwise_fma(-sum, rP, z[p]) * inv;
-            zo[p][2 * h] = (__bf16)o[0];
-            zo[p][2 * h + 1] = (__bf16)o[1];
+            const f32x2 r2 = {r[p][2 * h], r[p][2 * h + 1]};
+            z[p] = fisher_z_table(r2, tab);
         }
+        missed |= normalize_half<P, true>(z, h, zo);
     }
     return missed;
 }
@@ -223,7 +352,18 @@ __device__ __forceinline__ unsigned long long normalize_task(
 // bits: the same MFMAs on the same operands.
 static constexpr bool fs_has_ahead(int LP) { return LP <= 32; }
 
-template <int TP, int LP, bool AHEAD, bool FORCE>
+// launch_fcma_corr_gram_fused's fisher argument ("auto" / "table" /
+// "log").  TABLE: the unclamped normalize takes the Fisher z from the
+// LDS table above; the redo of a task with a miss is the clamped log
+// normalize as before.  One-k-step instances only: the LP = 64 instances
+// stand at 255 VGPRs and keep the logs.  The FORCE instances keep them
+// too and are the yardstick inside the build.
+#define FS_FISHER_AUTO 0
+#define FS_FISHER_TABLE 1
+#define FS_FISHER_LOG 2
+static constexpr bool fs_has_table(int LP) { return LP <= 32; }
+
+template <int TP, int LP, bool AHEAD, bool FORCE, bool TABLE>
 __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     const bf16_t* __restrict__ T1, const bf16_t* __restrict__ T2,
     float* __restrict__ Gout, ll VA, ll VB, ll s0, ll C, int nsplit,
@@ -234,6 +374,8 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     constexpr int KS = (LP + 31) / 32;         // MFMA k-steps
     constexpr int NT = 2 * SPW;                // tasks per window
     static_assert(!AHEAD || KS == 1, "AHEAD needs a one-k-step instance");
+    static_assert(!TABLE || (KS == 1 && !FORCE),
+                  "TABLE needs a one-k-step instance that finds its clamp");
 
     const ll vs = blockIdx.x % nsplit;
     const ll ct = blockIdx.x / nsplit;
@@ -252,8 +394,15 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     const int l16 = lane & 15;
     const int q = lane >> 4;
 
+    // one array, so that the table (TABLE only) starts at LDS address 0
+    // and the two z images follow it
+    constexpr unsigned TABB = TABLE ? FS_TAB_BYTES : 0;
     __shared__ __attribute__((aligned(16)))
-        unsigned char zbuf[2][FS_CB * FS_CSTRIDE];
+        unsigned char lds[TABB + 2 * FS_CB * FS_CSTRIDE];
+    if constexpr (TABLE) {
+        fisher_table_build((float*)lds, tid, 64 * FS_NW);
+        __syncthreads();
+    }
 
     // selected voxel of this lane (clamped: tail lanes recompute the
     // last voxel and are never stored)
@@ -324,7 +473,7 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     // so the swizzled chunk is fixed per lane and sub-tile: one base per
     // sub-tile, computed once, and the rest of the address is the
     // immediate offset of the ds_write
-    unsigned char* const zb = &zbuf[0][0];
+    unsigned char* const zb = lds + TABB;
     const int swz = ((wv * P) >> 2) & 3;
     unsigned st_base[2];
     #pragma unroll
@@ -453,24 +602,36 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
                         r[p] = corr_mfma<LP>(c2[p], sel[si][p][KS - 1],
                                              r[p]);
                 }
-                f32x4 rq[P];
-                quantize(r, rq);
                 // Clamp found after the fact: |rq| >= 1 (the diagonal of
                 // a self-correlation, duplicated voxels) is the only
                 // case in which the clamp of the Fisher z changes
                 // anything, and exactly there the unclamped normalize
                 // ends in a NaN variance.  Nobody looks for it ahead.
                 nbf16x4 zo[P];
-                if constexpr (FORCE) {
-                    normalize_task<P, true>(rq, zo);
-                } else {
+                if constexpr (TABLE) {
+                    // the lookup rounds r itself; the redo rebuilds the
+                    // rounded r in the cold path
                     const unsigned long long hit =
-                        normalize_task<P, false>(rq, zo);
-                    if constexpr (REDO_WINDOW) {
-                        missed |= hit;
+                        normalize_task_table<P>(r, lds, zo);
+                    if (__builtin_expect(hit != 0, 0)) {     // wave-uniform
+                        f32x4 rq[P];
+                        quantize(r, rq);
+                        normalize_task<P, true>(rq, zo);
+                    }
+                } else {
+                    f32x4 rq[P];
+                    quantize(r, rq);
+                    if constexpr (FORCE) {
+                        normalize_task<P, true>(rq, zo);
                     } else {
-                        if (__builtin_expect(hit != 0, 0))   // wave-uniform
-                            normalize_task<P, true>(rq, zo);
+                        const unsigned long long hit =
+                            normalize_task<P, false>(rq, zo);
+                        if constexpr (REDO_WINDOW) {
+                            missed |= hit;
+                        } else {
+                            if (__builtin_expect(hit != 0, 0))  // uniform
+                                normalize_task<P, true>(rq, zo);
+                        }
                     }
                 }
                 store_task(img, si, st, zo);
@@ -560,22 +721,31 @@ extern "C" int fcma_corr_gram_fused_vt(void) { return FS_VT; }
 extern "C" void launch_fcma_corr_gram_fused(
     const void* T1, const void* T2, float* Gout, int LP, ll VA, ll VB,
     ll s0, ll C, int P, int nsplit, int do_shrink, int force_clamp,
-    int schedule, hipStream_t stream) {
+    int schedule, int fisher, hipStream_t stream) {
     ll grid = ((C + FS_CB - 1) / FS_CB) * nsplit;
     // FS_SCHED_AUTO and FS_SCHED_AHEAD take the AHEAD order where the
     // instance has one, FS_SCHED_PHASED never does
     const bool ahead = schedule != FS_SCHED_PHASED;
+    // FS_FISHER_AUTO and FS_FISHER_TABLE take the table where the
+    // instance has one (fcma_corr_gram_fused_table), FS_FISHER_LOG never
+    const bool table = fisher != FS_FISHER_LOG && !force_clamp;
     // force_clamp picks the instance that runs the clamped normalize for
     // every task; the other one finds the tasks that need it afterwards
-    #define FS_LAUNCH_F(TP, TLP, TAHEAD, TFORCE)                         \
+    #define FS_LAUNCH_F(TP, TLP, TAHEAD, TFORCE, TTABLE)                 \
         hipLaunchKernelGGL(                                              \
-            (k_corr_gram_fused<TP, TLP, TAHEAD, TFORCE>),                \
+            (k_corr_gram_fused<TP, TLP, TAHEAD, TFORCE, TTABLE>),        \
             dim3(grid), dim3(64 * FS_NW), 0, stream, (const bf16_t*)T1,  \
             (const bf16_t*)T2, Gout, VA, VB, s0, C, nsplit, do_shrink)
     #define FS_LAUNCH(TP, TLP, TAHEAD)                                   \
         do {                                                             \
-            if (force_clamp) FS_LAUNCH_F(TP, TLP, TAHEAD, true);         \
-            else FS_LAUNCH_F(TP, TLP, TAHEAD, false);                    \
+            if constexpr (fs_has_table(TLP)) {                           \
+                if (table) {                                             \
+                    FS_LAUNCH_F(TP, TLP, TAHEAD, false, true);           \
+                    break;                                               \
+                }                                                        \
+            }                                                            \
+            if (force_clamp) FS_LAUNCH_F(TP, TLP, TAHEAD, true, false);  \
+            else FS_LAUNCH_F(TP, TLP, TAHEAD, false, false);             \
         } while (0)
     #define FS_ONE(TP, TLP)                                              \
         do {                                                             \
@@ -606,4 +776,49 @@ extern "C" void launch_fcma_corr_gram_fused(
 extern "C" int fcma_corr_gram_fused_ahead(int P, ll L) {
     (void)P;
     return fs_has_ahead(fused_lp(L));
+}
+
+// whether the (P, L) instance takes the Fisher z from the LDS table
+// (clamp "auto"; the clamp "always" instances never do)
+extern "C" int fcma_corr_gram_fused_table(int P, ll L) {
+    (void)P;
+    return fs_has_table(fused_lp(L));
+}
+
+// Tests only: the table as a workgroup builds it, and for n fp32 values
+// r (bf16 patterns widened) the z of the log path and of the lookup
+// (zTab[2][n]: r as the low and as the high half of a pair), through
+// the device functions the kernel runs.
+__global__ __launch_bounds__(64 * FS_NW) void k_fisher_table_probe(
+    const float* __restrict__ r, ll n, float* __restrict__ tabOut,
+    float* __restrict__ zLog, float* __restrict__ zTab) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[FS_TAB_BYTES];
+    const int tid = threadIdx.x;
+    fisher_table_build((float*)lds, tid, 64 * FS_NW);
+    __syncthreads();
+    if (blockIdx.x == 0)
+        for (int i = tid; i <= FS_TAB_LAST; i += 64 * FS_NW)
+            tabOut[i] = ((const float*)lds)[i];
+    for (ll i = (ll)blockIdx.x * (64 * FS_NW) + tid; i < n;
+         i += (ll)gridDim.x * (64 * FS_NW)) {
+        // r[i] through both halves of a pair (the low half takes its
+        // address from the v_mad_u32_u16, the high half from the
+        // shift), each time next to another value: zTab is [2][n]
+        const f32x2 r2 = {r[i], r[i]};
+        const float other = r[n - 1 - i];
+        zLog[i] = fisher_z_log<false>(r2)[0];
+        zTab[i] = fisher_z_table((f32x2){r[i], other}, lds)[0];
+        zTab[n + i] = fisher_z_table((f32x2){other, r[i]}, lds)[1];
+    }
+}
+
+extern "C" int fcma_fisher_table_entries(void) { return FS_TAB_LAST + 1; }
+
+extern "C" void launch_fcma_fisher_table_probe(
+    const float* r, ll n, float* tabOut, float* zLog, float* zTab,
+    hipStream_t stream) {
+    const int grid = (int)min((n + 64 * FS_NW - 1) / (64 * FS_NW), (ll)64);
+    hipLaunchKernelGGL(k_fisher_table_probe, dim3(max(grid, 1)),
+                       dim3(64 * FS_NW), 0, stream, r, n, tabOut, zLog,
+                       zTab);
 }
