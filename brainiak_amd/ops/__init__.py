@@ -249,6 +249,19 @@ def fcma_corr_gram_fused_table(P: int, L: int) -> bool:
     return bool(_ext().fcma_corr_gram_fused_table(int(P), int(L)))
 
 
+def fcma_fused_image_layout(P: int):
+    """Tests only: the layout of ``fcma_corr_gram_fused``'s z image in
+    LDS for P epochs per subject, from the address functions the kernel
+    runs, evaluated on the host (no launch).  Returns ``(stride,
+    image_bytes, table_bytes, store, read)``: the bytes from one voxel to
+    the next, the bytes of one image (two lie back to back, behind
+    ``table_bytes`` of Fisher table in the table instances), the int32
+    byte offsets ``store[wave, si, st, p, lane]`` of every 8-byte
+    ``ds_write_b64`` and ``read[voxel, band, lane]`` of every 16-byte
+    ``ds_read_b128`` of the Gram."""
+    return _ext().fcma_fused_image_layout(int(P))
+
+
 def fcma_corr_gram_fused_ahead(P: int, L: int) -> bool:
     """True when the ``fcma_corr_gram_fused`` instance for P epochs per
     subject and epoch length L has the ``"ahead"`` schedule."""

@@ -45,6 +45,7 @@ int fcma_corr_gram_fused_table(int, ll);
 void launch_fcma_corr_gram_fused(const void*, const void*, float*, int, ll,
                                  ll, ll, ll, int, int, int, int, int, int,
                                  void*);
+void fcma_fused_image_layout(int, int*, int*, int*);
 int fcma_fisher_table_entries(void);
 void launch_fcma_fisher_table_probe(const float*, ll, float*, float*,
                                     float*, void*);
@@ -543,6 +544,22 @@ std::vector<torch::Tensor> fcma_fisher_table_probe(torch::Tensor r) {
                                    zlog.data_ptr<float>(),
                                    ztab.data_ptr<float>(), cur_stream());
     return {tab, zlog, ztab};
+}
+
+// Tests only.  The layout of the fused kernel's z image in LDS from the
+// address functions the kernel runs, evaluated on the host: (stride,
+// image bytes, LDS bytes ahead of the first image in the table instances,
+// store offsets int32 [8, 64/P/8, 2, P, 64] by (wave, si, st, p, lane),
+// read offsets int32 [16, 4, 64] by (voxel, band, lane)).
+std::tuple<int64_t, int64_t, int64_t, torch::Tensor, torch::Tensor>
+fcma_fused_image_layout_py(int64_t P) {
+    TORCH_CHECK(P == 2 || P == 4, "fused path needs P in {2,4}");
+    auto store = torch::empty({8, 64 / P / 8, 2, P, 64}, torch::kInt32);
+    auto read = torch::empty({16, 4, 64}, torch::kInt32);
+    int dims[3];
+    fcma_fused_image_layout((int)P, dims, store.data_ptr<int>(),
+                            read.data_ptr<int>());
+    return {dims[0], dims[1], dims[2], store, read};
 }
 
 bool fcma_fused_gram_native(int64_t E, int64_t P, int64_t L) {
@@ -1175,6 +1192,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "table (clamp \"auto\")");
     m.def("fcma_fisher_table_probe", &fcma_fisher_table_probe,
           "tests only: (table, log-path z, lookup z) for fp32 values r");
+    m.def("fcma_fused_image_layout", &fcma_fused_image_layout_py,
+          "tests only: (stride, image bytes, table bytes, store offsets, "
+          "read offsets) of the fused kernel's z image in LDS",
+          py::arg("P"));
     m.def("fcma_corr_gram_fused_ahead",
           [](int64_t P, int64_t L) {
               return fcma_corr_gram_fused_ahead((int)P, L) != 0;

@@ -65,22 +65,30 @@
 // because window w+2 overwrites that image.  Here the reads sit right
 // behind the barrier of window w, ahead of every store of window w+1.
 //
-// LDS image: row (c, e) is 64 B = four 16-B chunks, chunk index XORed
-// with (e>>2)&3 so the Gram's ds_read_b128 (16 rows x one chunk per
-// 16-lane group) touches 16 distinct slots; the per-voxel stride is
-// 4096 + 32 B so the 16 voxels of a phase-2 store spread over the banks.
+// LDS image: voxel c at c * stride, row (c, e) 64 B = four 16-B chunks,
+// chunk k in slot k ^ fs_img_swz(e).  The address functions, and what
+// the banking of gfx950 asks of them, are in fcma_fused_image.h: a
+// phase-2 ds_write_b64 is served in four contiguous 16-lane groups on
+// banks (a/4) mod 32 (one group = the 16 voxels: the stride of
+// 4096 + 16 B leaves it 2-way, the floor for this store), a Gram
+// ds_read_b128 in four NON-contiguous 16-lane groups on banks
+// (a/4) mod 64 (the swizzle 0, 3, 2, 1 of (e>>2)&3 makes each
+// conflict-free).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
 #include "fcma_common.h"
+#include "fcma_fused_image.h"
 
 #define FS_CB 16
 #define FS_VT 32
 #define FS_E 64
 #define FS_NW 8                                // waves per workgroup
 #define FS_VPW (FS_CB / FS_NW)                 // Gram voxels per wave
-#define FS_CSTRIDE (FS_E * FS_VT * 2 + 32)     // bytes per voxel image
+// the z image's strides and offsets: fcma_fused_image.h
+static_assert(FS_CB == FS_IMG_CB && FS_E == FS_IMG_E && FS_NW == FS_IMG_NW
+              && FS_VT * 2 == FS_IMG_ROWB, "fcma_fused_image.h");
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 nbf16x2 __attribute__((ext_vector_type(2)));
@@ -398,7 +406,7 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     // and the two z images follow it
     constexpr unsigned TABB = TABLE ? FS_TAB_BYTES : 0;
     __shared__ __attribute__((aligned(16)))
-        unsigned char lds[TABB + 2 * FS_CB * FS_CSTRIDE];
+        unsigned char lds[TABB + 2 * fs_img_bytes()];
     if constexpr (TABLE) {
         fisher_table_build((float*)lds, tid, 64 * FS_NW);
         __syncthreads();
@@ -466,26 +474,21 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
     };
 
     // 8-byte store of a task: columns st*16 + 4q .. +3 of rows (c, e),
-    // e = (wv + FS_NW*si)*P + p, into the image at byte offset img
-    // into the image at byte offset img: row e at e * 64, chunk
-    // st*2 + (q>>1) XORed with (e >> 2) & 3.  That XOR term does not
-    // depend on si or p (FS_NW*si*P is a multiple of 16 and p < P <= 4),
-    // so the swizzled chunk is fixed per lane and sub-tile: one base per
-    // sub-tile, computed once, and the rest of the address is the
-    // immediate offset of the ds_write
+    // e = (wv + FS_NW*si)*P + p, into the image at byte offset img.  The
+    // swizzled chunk is fixed per lane and sub-tile (fcma_fused_image.h):
+    // one base per sub-tile, computed once, and the rest of the address
+    // is the immediate offset of the ds_write
     unsigned char* const zb = lds + TABB;
-    const int swz = ((wv * P) >> 2) & 3;
     unsigned st_base[2];
     #pragma unroll
     for (int st = 0; st < 2; ++st)
-        st_base[st] = l16 * FS_CSTRIDE + wv * P * 64
-            + (((st * 2 + (q >> 1)) ^ swz) << 4) + (q & 1) * 8;
+        st_base[st] = fs_img_store_base(P, wv, st, lane);
     auto store_task = [&](unsigned img, int si, int st,
                           const nbf16x4 (&zo)[P]) {
         unsigned char* dst = zb + (img + st_base[st]);
         #pragma unroll
         for (int p = 0; p < P; ++p)
-            *(nbf16x4*)(dst + (si * FS_NW * P + p) * 64) = zo[p];
+            *(nbf16x4*)(dst + fs_img_store_step(P, si, p)) = zo[p];
     };
 
     // the wave's SPW x P (x KS) selected-voxel fragments do not depend
@@ -558,7 +561,7 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
 
     for (ll w = w0; w < w1; ++w) {
         const ll v0 = w * FS_VT;
-        const unsigned img = (unsigned)((w - w0) & 1) * (FS_CB * FS_CSTRIDE);
+        const unsigned img = (unsigned)((w - w0) & 1) * fs_img_bytes();
         unsigned char* zimg = zb + img;
         // lanes whose unclamped normalize met a 1 +- r <= 0, OR-ed over
         // the tasks of the window
@@ -651,15 +654,11 @@ __global__ __launch_bounds__(64 * FS_NW) void k_corr_gram_fused(
 
         #pragma unroll
         for (int i = 0; i < FS_VPW; ++i) {
-            const unsigned char* zc =
-                zimg + (wv * FS_VPW + i) * FS_CSTRIDE;
             nbf16x8 f[4];
             #pragma unroll
-            for (int bnd = 0; bnd < 4; ++bnd) {
-                const int e = bnd * 16 + l16;
+            for (int bnd = 0; bnd < 4; ++bnd)
                 f[bnd] = *(const nbf16x8*)(
-                    zc + e * 64 + ((q ^ ((e >> 2) & 3)) << 4));
-            }
+                    zimg + fs_img_read_offset(wv * FS_VPW + i, bnd, lane));
             int t = 0;
             #pragma unroll
             for (int bi = 0; bi < 4; ++bi)
@@ -783,6 +782,30 @@ extern "C" int fcma_corr_gram_fused_ahead(int P, ll L) {
 extern "C" int fcma_corr_gram_fused_table(int P, ll L) {
     (void)P;
     return fs_has_table(fused_lp(L));
+}
+
+// Tests only: the z image's layout from the functions the kernel runs
+// (fcma_fused_image.h), on the host.  dims = {stride, image bytes, LDS
+// bytes ahead of the first image in the table instances};
+// store[wave][si][st][p][lane] (si < 64 / P / 8) and
+// read[voxel][band][lane] are byte offsets into one image.
+extern "C" void fcma_fused_image_layout(int P, int* dims, int* store,
+                                        int* read) {
+    dims[0] = (int)fs_img_stride();
+    dims[1] = (int)fs_img_bytes();
+    dims[2] = FS_TAB_BYTES;
+    const int SPW = FS_E / P / FS_NW;
+    for (int wv = 0; wv < FS_NW; ++wv)
+        for (int si = 0; si < SPW; ++si)
+            for (int st = 0; st < 2; ++st)
+                for (int p = 0; p < P; ++p)
+                    for (int lane = 0; lane < 64; ++lane)
+                        *store++ = (int)fs_img_store_offset(P, wv, si, st,
+                                                            p, lane);
+    for (int c = 0; c < FS_CB; ++c)
+        for (int bnd = 0; bnd < 4; ++bnd)
+            for (int lane = 0; lane < 64; ++lane)
+                *read++ = (int)fs_img_read_offset(c, bnd, lane);
 }
 
 // Tests only: the table as a workgroup builds it, and for n fp32 values
